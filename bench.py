@@ -10,12 +10,12 @@ histogram update) for every object of the batch on the next synthetic frame.  Co
   --config synth512 (configs[3]) 512 synthetic objects (random sparse viewpoint models), Region + Depth, sharded
                     over the GPUs (strong scaling: 512 / N objects per GPU).
   --config chain8   (configs[4]) kinematic chain of 8 bodies / 13 dof tracked by 8 RegionModalities, the structure's
-                    joint Hessian summed over the GPUs with ONE all-reduce per Newton step; plus the sweep over
-                    1..50 bodies of examples/optimization_time.cpp.
+                    joint Hessian summed over the GPUs with ONE all-reduce per Newton step; with --full also the
+                    sweep over 1..50 bodies of examples/optimization_time.cpp.
 
 Frames, models and histograms are resident in HBM before the timed region starts (the reference's evaluators also
-exclude image loading, rbot_evaluator.cpp:354-414).  Prints ONE JSON line on rank 0 (roofline,
-cpu_baseline and parity blocks).
+exclude image loading, rbot_evaluator.cpp:354-414).  Prints ONE JSON line on rank 0; with --full it also carries the
+roofline, cpu_baseline and parity blocks, without it they are null.
 """
 import argparse
 import ctypes as C
@@ -65,6 +65,34 @@ CONFIGS = {
                               "points), Region + Depth, YCB parameters, every object its own 640x480 frame ring "
                               "(64 distinct rendered streams)"),
 }
+# distinct frames per object stream that are rendered and staged on the device (frame 0 starts the modalities): a run of
+# more steps walks back and forth over the staged frames (frame_of_step), so that neither the setup time nor the device
+# memory grows with --steps; every step still tracks a new frame, one step of the synthetic motion away from the last
+MAX_FRAMES = 32
+
+
+def frame_of_step(k, n_staged):
+    """the staged frame step k looks at: k itself while k < n_staged, then n_staged - 2, ..., 1, 2, ... (the motion
+    between consecutive frames stays the synthetic trajectory's, only its direction turns)"""
+    if k < n_staged:
+        return k
+    period = 2 * (n_staged - 2)
+    j = (k - 1) % period
+    return 1 + j if j <= n_staged - 2 else 1 + period - j
+
+
+def walk_frames(inputs, n_frames):
+    """`inputs` (its n_frames rendered frames) as a sequence of n_frames frames in the order of frame_of_step: the frame
+    and ground-truth lists hold references to the rendered ones, no copies"""
+    if n_frames <= inputs.n_frames:
+        return inputs
+    idx = [frame_of_step(k, inputs.n_frames) for k in range(n_frames)]
+    walked = type(inputs).__new__(type(inputs))
+    walked.__dict__.update(inputs.__dict__)
+    walked.n_frames = n_frames
+    for name in ("gt", "color", "depth"):
+        walked.__dict__[name] = [[seq[j] for j in idx] for seq in inputs.__dict__[name]]
+    return walked
 
 
 def parse():
@@ -79,11 +107,21 @@ def parse():
     p.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU baseline sample budget (1 thread)")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--no-cpu-parallel", action="store_true", help="skip the all-cores (OpenMP) CPU leg")
+    p.add_argument("--full", action="store_true",
+                   help="also everything beyond the headline: the roofline leg (HIP events), the CPU baselines and the "
+                        "parity check against the oracle, the unfused device buckets, the host-buffer legs, the timed "
+                        "region repeated per --repeats / --busy-seconds; chain8: also the distributed path at world size "
+                        "1 and the optimization-time sweep.  Without it a run sets up, warms up, times --steps steps "
+                        "ONCE, writes --dump-outputs and prints the line")
+    p.add_argument("--dump-outputs", metavar="DIR", default="",
+                   help="after the timed steps, write what they computed (every object's body2world pose after the last "
+                        "timed step -- of the first timed region when --full repeats it --, float32) as DIR/<name>.npy")
     p.add_argument("--repeats", type=int, default=0,
-                   help="how often the timed region of K steps is repeated; 0 = until --busy-seconds of timed regions")
+                   help="how often the timed region of K steps is repeated; 0 = once, with --full until --busy-seconds "
+                        "of timed regions")
     p.add_argument("--busy-seconds", type=float, default=6.0,
-                   help="with --repeats 0: keep repeating the K-step region until this much GPU time has been timed "
-                        "(at least 5 regions): a K = 20 region lasts ~3 ms, too short for device-level telemetry")
+                   help="with --full and --repeats 0: keep repeating the K-step region until this much GPU time has been "
+                        "timed (at least 5 regions): a K = 20 region lasts ~3 ms, too short for device-level telemetry")
     p.add_argument("--no-pcie", action="store_true", help="skip the host-buffer (PCIe-inclusive) legs")
     p.add_argument("--no-buckets", action="store_true",
                    help="skip the one-launch-per-sub-step leg (profiling runs: only the timed kernels are launched)")
@@ -137,7 +175,7 @@ def launch_ranks(n_gpus, argv, n_visible=None):
     """`python bench.py --gpus N` without a launcher: re-run this command line as N ranks, one per GPU, under
     torch.distributed.run on 127.0.0.1 (what the driver does itself for its scaling runs).  Fails loudly when fewer
     than N devices are visible -- a run that asked for N GPUs never reports a smaller n_gpus.  Returns the launcher's
-    command line (the caller execs it)."""
+    command line (the caller runs it as a child process)."""
     n_visible = visible_gpus() if n_visible is None else n_visible
     if share_one_gpu() and n_visible >= 1:
         n_visible = n_gpus
@@ -243,6 +281,19 @@ def rank_share_points(pkg, scenes, inputs_full, cfg, config, counts, objects, mo
             "steps": K, "warmup": W, "regions": regions, "points": points}
 
 
+def write_outputs(directory, arrays, limit_bytes=64 << 20):
+    """--dump-outputs: the arrays a caller of the timed path receives, one DIR/<name>.npy each (float32 / float64), at
+    most `limit_bytes` in all -- two builds run with the same arguments can be compared output for output"""
+    arrays = {name: np.ascontiguousarray(a) for name, a in arrays.items()}
+    assert all(a.dtype in (np.float32, np.float64) for a in arrays.values()), {n: a.dtype for n, a in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > limit_bytes:
+        raise SystemExit("bench.py --dump-outputs: %d bytes of outputs, more than %d" % (total, limit_bytes))
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
+
+
 def flush_stdio():
     sys.stdout.flush()
     try:
@@ -254,22 +305,27 @@ def flush_stdio():
 def main():
     args = parse()
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
+        # a child process, never os.exec*: this process has opened the GPU (launch_ranks counts the devices)
+        import subprocess
         cmd = launch_ranks(args.gpus, sys.argv[1:])
-        os.execv(cmd[0], cmd)
+        rc = subprocess.call(cmd)
+        sys.exit(rc if rc >= 0 else 128 - rc)
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if world != args.gpus:
         raise SystemExit("bench.py: --gpus %d but the launcher started %d rank(s) (WORLD_SIZE)" % (args.gpus, world))
-    import torch
-    assert torch.cuda.is_available(), "bench.py needs an MI355X"
     dry_run = share_one_gpu() and world > 1
     if dry_run:
         local_rank = 0  # (chain8: RCCL refuses two ranks on one device -- the link sums cross over gloo, bench_chain.run)
-    if torch.cuda.device_count() <= local_rank:
-        raise SystemExit("bench.py: rank %d has no GPU (%d visible)" % (rank, torch.cuda.device_count()))
-    dist = None
+    # torch carries the collectives of N > 1 ranks and nothing else: one rank runs on the library's own HIP runtime
+    # (pkg.open_context fails loudly without a GPU), without a second runtime and torch's start-up in the process
+    torch, dist = None, None
     if world > 1:
+        import torch
+        assert torch.cuda.is_available(), "bench.py needs an MI355X"
+        if torch.cuda.device_count() <= local_rank:
+            raise SystemExit("bench.py: rank %d has no GPU (%d visible)" % (rank, torch.cuda.device_count()))
         import torch.distributed as dist
         torch.cuda.set_device(local_rank)
         if dry_run:
@@ -323,27 +379,29 @@ def run_objects(args, pkg, scenes, rank, local_rank, world, dist, torch, dry_run
         hip.call("set_object_split", 0)
     K, W = args.steps, args.warmup
     n_frames = K + W + 1
+    n_staged = min(n_frames, MAX_FRAMES)
     use_depth = cfg["with_depth"]
     t0 = time.time()
     plan = rank_plan(args.config, rank, world, args.objects, args.models)
     n_obj, total_objects, n_streams, n_models = plan["n_obj"], plan["total_objects"], plan["n_streams"], plan["n_models"]
-    base = scenes.Inputs(n_streams, n_frames, n_divides=args.n_divides, n_models=n_models, with_depth=use_depth,
+    base = scenes.Inputs(n_streams, n_staged, n_divides=args.n_divides, n_models=n_models, with_depth=use_depth,
                          first_object=plan["first_object"])
+    base = walk_frames(base, n_frames)  # (frames 0 .. W + K; the host-side legs index them by step)
     inputs = scenes.replicate(base, n_obj)
     inst = scenes.Instance(hip, inputs, use_depth=use_depth)
-    scenes.stage_frames(hip, inst, inputs, n_frames)
+    scenes.stage_frames(hip, inst, inputs, n_staged)
     setup_s = time.time() - t0
 
     def barrier():
         hip.call("sync")
-        torch.cuda.synchronize()
         if dist is not None:
+            torch.cuda.synchronize()
             dist.barrier()
-        torch.cuda.synchronize()
+            torch.cuda.synchronize()
 
     def run(first_frame, count):
         for k in range(first_frame, first_frame + count):
-            hip.call("cameras_select_slot", k)
+            hip.call("cameras_select_slot", frame_of_step(k, n_staged))
             hip.call("execute_tracking_step", k)
 
     def get_poses():
@@ -365,7 +423,9 @@ def run_objects(args, pkg, scenes, rank, local_rank, world, dist, torch, dry_run
     times = [elapsed]
     restart = np.stack([np.ascontiguousarray(inputs.gt[i][W].T, np.float32).reshape(16) for i in range(n_obj)])
     # (every rank repeats the same number of times: the count is fixed from rank 0's first region)
-    n_repeats = args.repeats if args.repeats > 0 else int(min(4000, max(5, args.busy_seconds / max(elapsed, 1e-6))))
+    n_repeats = args.repeats if args.repeats > 0 else 1
+    if args.full and args.repeats <= 0:
+        n_repeats = int(min(4000, max(5, args.busy_seconds / max(elapsed, 1e-6))))
     if dist is not None:
         tn = torch.tensor([n_repeats], device="cuda")
         dist.broadcast(tn, 0)
@@ -378,6 +438,11 @@ def run_objects(args, pkg, scenes, rank, local_rank, world, dist, torch, dry_run
         barrier()
         times.append(pkg.sharding.max_over_ranks(time.perf_counter() - t, dist, device="cuda"))
     elapsed = float(np.median(times))
+    if args.dump_outputs:  # the first timed trajectory (the one checked below): the same bits in every run
+        mine = np.stack([poses[i].reshape(4, 4).T for i in range(n_obj)])
+        everyone = pkg.sharding.gather_poses(plan["global_ids"], mine, total_objects, dist)  # (global object order)
+        if rank == 0:
+            write_outputs(args.dump_outputs, {"body2world_poses": everyone})
     tracked, adds_gt = 0, []
     for i in range(n_obj):
         e = syn.pose_errors(poses[i].reshape(4, 4).T, inputs.gt[i][W + K])
@@ -387,7 +452,7 @@ def run_objects(args, pkg, scenes, rank, local_rank, world, dist, torch, dry_run
 
     # ---- roofline leg: HIP events around the kernels on the context stream (rank 0) ----
     roofline = None
-    if rank == 0:
+    if rank == 0 and args.full:
         # (a) ONE event pair around the K launches of a timed region (nothing between the launches): the device time
         # per launch, which is what `achieved` is computed from; (b) an event pair around every launch, as round 3
         # measured it: each pair also times the launch gap in front of its kernel and the markers slow the stream, so
@@ -439,15 +504,15 @@ def run_objects(args, pkg, scenes, rank, local_rank, world, dist, torch, dry_run
     # ---- the evaluators' four time buckets (rbot_evaluator.cpp:354-414) on the device, one launch per sub-step
     # (m3t_hip_set_fused_step(0)), each bucket synchronised and timed on the host: what the fused launch replaces ----
     buckets = None
-    if rank == 0 and world == 1 and args.config in ("rbot64", "ycb21") and not args.no_buckets:
+    if rank == 0 and world == 1 and args.config in ("rbot64", "ycb21") and args.full and not args.no_buckets:
         try:  # (extra legs never cost the line: the headline above is already measured)
-            buckets = device_buckets(hip, restart, n_obj, W, min(K, 5), cfg)
+            buckets = device_buckets(hip, restart, n_obj, W, min(K, 5), cfg, n_staged)
         except Exception as e:  # noqa: BLE001
             buckets = {"error": str(e)[:300]}
 
     # ---- host-buffer (PCIe-inclusive) rate: every step first receives its frames from host memory; never `value` ----
     pcie = None
-    if rank == 0 and world == 1 and args.config == "rbot64" and not args.no_pcie:
+    if rank == 0 and world == 1 and args.config == "rbot64" and args.full and not args.no_pcie:
         try:
             pcie = pcie_legs(hip, inst, inputs, n_obj, W, K)
         except Exception as e:  # noqa: BLE001
@@ -462,7 +527,7 @@ def run_objects(args, pkg, scenes, rank, local_rank, world, dist, torch, dry_run
     # ---- CPU baseline: the oracle restatement, bounded sample (rank 0); its first pass over the frames is also
     # the parity check of the benchmarked trajectory: the same objects, the same frames, free running ----
     cpu, parity = None, None
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         # N > 1: rank 0 still checks its own first objects against the oracle and times a short 1-thread sample (the
         # other ranks wait at the final barrier); the all-cores and native-build legs run at N = 1 only
         if world > 1:
@@ -579,7 +644,7 @@ def run_objects(args, pkg, scenes, rank, local_rank, world, dist, torch, dry_run
     return out
 
 
-def device_buckets(hip, restart, n_obj, W, K, cfg):
+def device_buckets(hip, restart, n_obj, W, K, cfg, n_staged):
     n_corr, n_update = (7, 2) if cfg["newton"] == 14 else (4, 2)
     hip.call("bodies_set_poses", restart.ctypes.data_as(C.POINTER(C.c_float)), n_obj)
     hip.call("set_fused_step", 0)
@@ -592,7 +657,7 @@ def device_buckets(hip, restart, n_obj, W, K, cfg):
         t[i] += time.perf_counter() - t0
 
     for k in range(1 + W, 1 + W + K):
-        hip.call("cameras_select_slot", k)
+        hip.call("cameras_select_slot", frame_of_step(k, n_staged))
         for c in range(n_corr):
             timed(0, "calculate_correspondences", k, c)
             for u in range(n_update):

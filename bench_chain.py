@@ -3,7 +3,7 @@
 tree but only the modalities of its own bodies (body i -> rank i mod N), and each Newton step sums the stacked link
 sums (6 + 36 floats per link) with ONE ncclAllReduce inside the library (m3t_hip_comm_init_rank: while a communicator
 is set, ExecuteTrackingStep runs link sums -> all-reduce -> project + solve by itself; the sum is exact, N ranks
-compute the poses of one process bit for bit).  Also the sweep of
+compute the poses of one process bit for bit).  With --full also the sweep of
 examples/optimization_time.cpp:14-79: Optimizer::CalculateOptimization for chains of 1..50 one-dof links."""
 import ctypes as C
 import os
@@ -208,13 +208,19 @@ def thread_ranks_chain(pkg, syn, host, inputs, joints, start_root, start_angles,
 
 
 def run(args, pkg, rank, local_rank, world, dist, torch, open_oracle, measured_traffic=None, dry_run=False):
+    import bench
     import bench_inputs as scenes
     syn, host = pkg.synthetic, pkg.host
     n_bodies, K, W = args.objects or 8, args.steps, args.warmup
     n_frames = K + W + 1
+    n_staged = min(n_frames, bench.MAX_FRAMES)  # (bench.frame_of_step: a longer run walks back and forth over them)
     n_div = min(args.n_divides, 2)  # the link kernels, not the model size, are the subject of this leg
     t0 = time.time()
-    inputs, joints, gt = chain_inputs(scenes, syn, n_bodies, n_frames, n_div)
+    inputs, joints, gt = chain_inputs(scenes, syn, n_bodies, n_staged, n_div)
+    if n_frames > n_staged:  # frames and ground truth of steps 0 .. W + K (references to the staged ones)
+        idx = [bench.frame_of_step(k, n_staged) for k in range(n_frames)]
+        inputs.color = [[seq[j] for j in idx] for seq in inputs.color]
+        gt = [gt[j] for j in idx]
     start_root = syn.perturb_pose(gt[0][0][0], np.random.default_rng(5), rot_deg=0.5, trans=0.001)
     start_angles = gt[0][1] + 0.01
     hip = pkg.open_context(local_rank)
@@ -233,22 +239,22 @@ def run(args, pkg, rank, local_rank, world, dist, torch, open_oracle, measured_t
         raw = bytes(uid.cpu().tolist())
         hip.call("comm_init_rank", C.create_string_buffer(raw, 128), 128, world, rank)
     for cam_i in owned:
-        hip.call("camera_set_ring", ch.cams[cam_i].id, n_frames)
-        for k in range(n_frames):
+        hip.call("camera_set_ring", ch.cams[cam_i].id, n_staged)
+        for k in range(n_staged):
             f = inputs.color[cam_i][k]
             hip.call("camera_upload_slot", ch.cams[cam_i].id, k, f.ctypes.data_as(C.c_void_p), f.strides[0])
     setup_s = time.time() - t0
 
     def barrier():
         hip.call("sync")
-        torch.cuda.synchronize()
         if dist is not None:
+            torch.cuda.synchronize()
             dist.barrier()
-        torch.cuda.synchronize()
+            torch.cuda.synchronize()
 
     def run_steps(first, count):
         for k in range(first, first + count):
-            hip.call("cameras_select_slot", k)
+            hip.call("cameras_select_slot", bench.frame_of_step(k, n_staged))
             hip.call("execute_tracking_step", k)
 
     hip.call("cameras_select_slot", 0)
@@ -265,21 +271,24 @@ def run(args, pkg, rank, local_rank, world, dist, torch, open_oracle, measured_t
         if first_poses is None:
             first_poses = ch.poses()
     elapsed = float(np.median(times))
-    # roofline leg: ONE HIP event pair on the context's stream around the K launches of one more region.  EVERY rank
-    # runs these steps: at N > 1 each of them reduces 14 times per step, and a rank that had already left for the final
-    # barrier would leave rank 0 waiting in its first all-reduce for ever (found by the two-rank dry run of round 6)
+    if args.dump_outputs and rank == 0:  # (every rank holds the whole link tree: rank 0's poses are all of them)
+        bench.write_outputs(args.dump_outputs, {"body2world_poses": np.asarray(first_poses, np.float32)})
+    # roofline leg (--full): ONE HIP event pair on the context's stream around the K launches of one more region.  EVERY
+    # rank runs these steps: at N > 1 each of them reduces 14 times per step, and a rank that had already left for the
+    # final barrier would leave rank 0 waiting in its first all-reduce for ever (found by the two-rank dry run of round 6)
     ms, cnt = (C.c_float * 2)(), (C.c_int * 2)()
-    hip.call("set_kernel_timing", 2)
-    run_steps(1 + W, K)
-    hip.call("get_kernel_timing", ms, cnt)
-    hip.call("set_kernel_timing", 0)
-    barrier()
+    if args.full:
+        hip.call("set_kernel_timing", 2)
+        run_steps(1 + W, K)
+        hip.call("get_kernel_timing", ms, cnt)
+        hip.call("set_kernel_timing", 0)
+        barrier()
     if rank != 0:
         return None
     kernel_ms = float(ms[0]) / max(int(cnt[0]), 1) if cnt[0] else None
     # ---- CPU restatement of the same chain (all bodies in one process) + parity of the first timed trajectory ----
     cpu, parity = None, None
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         ora = open_oracle()
         oc = Chain(ora, host, syn, inputs, joints, start_root, start_angles, range(n_bodies))
         oc.upload(inputs, 0)
@@ -303,7 +312,7 @@ def run(args, pkg, rank, local_rank, world, dist, torch, open_oracle, measured_t
     # library's ncclAllReduce -> project + solve, one launch per sub-step (what N > 1 costs per rank before the
     # transport's latency is added); the poses must be the fused launch's
     distributed = None
-    if world == 1:
+    if world == 1 and args.full:
         try:
             ctx2 = pkg.open_context(local_rank)
             ch2 = Chain(ctx2, host, syn, inputs, joints, start_root, start_angles, range(n_bodies))
@@ -311,8 +320,8 @@ def run(args, pkg, rank, local_rank, world, dist, torch, open_oracle, measured_t
             ctx2.call("comm_get_unique_id", buf, 128)
             ctx2.call("comm_init_rank", buf, 128, 1, 0)
             for cam in ch2.cams:
-                ctx2.call("camera_set_ring", cam.id, n_frames)
-                for k in range(n_frames):
+                ctx2.call("camera_set_ring", cam.id, n_staged)
+                for k in range(n_staged):
                     f = inputs.color[ch2.cams.index(cam)][k]
                     ctx2.call("camera_upload_slot", cam.id, k, f.ctypes.data_as(C.c_void_p), f.strides[0])
             ctx2.call("cameras_select_slot", 0)
@@ -320,7 +329,7 @@ def run(args, pkg, rank, local_rank, world, dist, torch, open_oracle, measured_t
 
             def steps2(first, count):
                 for k in range(first, first + count):
-                    ctx2.call("cameras_select_slot", k)
+                    ctx2.call("cameras_select_slot", bench.frame_of_step(k, n_staged))
                     ctx2.call("execute_tracking_step", k)
             steps2(1, W)
             ctx2.call("sync")
@@ -343,7 +352,7 @@ def run(args, pkg, rank, local_rank, world, dist, torch, open_oracle, measured_t
     # ---- examples/optimization_time.cpp: CalculateOptimization for chains of 1..50 one-dof links ----
     sweep = []
     n_structures = 256
-    for nb in (1, 2, 4, 8, 16, 32, 50):
+    for nb in ((1, 2, 4, 8, 16, 32, 50) if args.full else ()):
         api = pkg.open_context(local_rank)
         tracker = optimization_time_structures(api, host, nb, n_structures)
         assert tracker.CalculateOptimization(0, 0, 0)
@@ -365,20 +374,33 @@ def run(args, pkg, rank, local_rank, world, dist, torch, open_oracle, measured_t
                       "gpu_us_per_structure": round(gpu_us / n_structures, 3), "cpu_port_us_per_structure": round(cpu_us, 2)})
     total = n_bodies * K
     rate = total / elapsed
-    import bench
     rccl_ranks = bench.live_rccl_ranks(dist, hip)  # ncclCommCount of the library's communicator: 0 at N = 1 (none set)
     projected = rank_share_chain(args, pkg, scenes, syn, host, inputs, joints, start_root, start_angles, n_bodies, local_rank) \
         if (getattr(args, "rank_share", "") and world == 1) else None
     collectives = C.c_longlong(0)  # ncclAllReduce calls this rank's context issued (start to here: W + repeats x K steps)
     hip.call("comm_get_allreduce_count", C.byref(collectives))
-    steps_run = W + max(1, args.repeats) * K + K  # (+ the roofline leg's region)
+    steps_run = W + max(1, args.repeats) * K + (K if args.full else 0)  # (+ the roofline leg's region)
     name = C.create_string_buffer(64)
     hip.call("get_step_kernel", name, 64)
     kernel = name.value.decode()
     shape = (C.c_int * 4)()
     hip.call("get_step_shape", shape)
     fused = kernel in ("tracking_step_tree_kernel", "tracking_step_tree_split_kernel")
-    traffic, traffic_src = (measured_traffic("chain8", kernel, n_bodies, True) if (measured_traffic and fused) else (None, None))
+    roofline = None
+    if args.full:
+        traffic, traffic_src = (measured_traffic("chain8", kernel, n_bodies, True) if (measured_traffic and fused)
+                                else (None, None))
+        roofline = {"bound": "hbm",
+                    "kernel": kernel if fused else "whole step: 7 x (correspondence + 2 x (g/H, project, solve)) + results launches",
+                    "achieved": round((n_bodies * B_ALG / (kernel_ms * 1e-3) / 1e9) if (fused and kernel_ms) else rate * B_ALG / 1e9, 3),
+                    "peak": 8000.0, "unit": "GB/s",
+                    "frac": round(((n_bodies * B_ALG / (kernel_ms * 1e-3)) if (fused and kernel_ms) else rate * B_ALG) / 8e12, 6),
+                    "kernel_ms": round(kernel_ms, 4) if (fused and kernel_ms) else None,
+                    "algorithmic_bytes_per_launch": n_bodies * B_ALG,
+                    "traffic": traffic, "traffic_source": traffic_src,
+                    "note": ("latency-bound by construction: 14 dependent solves of one 13-dof structure per frame, each on "
+                             "one wave" if fused else
+                             "launch- and latency-bound by construction: 50 dependent launches per frame for one structure")}
     return {
         "metric": "pose-updates/sec (Mb-ICG kinematic chain, %d bodies, %d dof)" % (n_bodies, 6 + n_bodies - 1),
         "value": round(rate, 1), "unit": "pose-updates/s", "n_gpus": world, "steps": K, "warmup": W,
@@ -398,17 +420,7 @@ def run(args, pkg, rank, local_rank, world, dist, torch, open_oracle, measured_t
                    "allreduce_calls_per_step": round(collectives.value / steps_run, 3),
                    "max_rotation_error_vs_ground_truth_rad": round(float(max(e[0] for e in gt_err)), 5),
                    "setup_s": round(setup_s, 1)},
-        "roofline": {"bound": "hbm",
-                     "kernel": kernel if fused else "whole step: 7 x (correspondence + 2 x (g/H, project, solve)) + results launches",
-                     "achieved": round((n_bodies * B_ALG / (kernel_ms * 1e-3) / 1e9) if (fused and kernel_ms) else rate * B_ALG / 1e9, 3),
-                     "peak": 8000.0, "unit": "GB/s",
-                     "frac": round(((n_bodies * B_ALG / (kernel_ms * 1e-3)) if (fused and kernel_ms) else rate * B_ALG) / 8e12, 6),
-                     "kernel_ms": round(kernel_ms, 4) if (fused and kernel_ms) else None,
-                     "algorithmic_bytes_per_launch": n_bodies * B_ALG,
-                     "traffic": traffic, "traffic_source": traffic_src,
-                     "note": ("latency-bound by construction: 14 dependent solves of one 13-dof structure per frame, each on "
-                              "one wave" if fused else
-                              "launch- and latency-bound by construction: 50 dependent launches per frame for one structure")},
+        "roofline": roofline,
         "cpu_baseline": cpu, "parity": parity,
         "repeats": {"n": len(times), "ms_per_step_min": round(min(times) / K * 1e3, 4),
                     "ms_per_step_median": round(elapsed / K * 1e3, 4)},

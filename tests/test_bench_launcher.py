@@ -5,6 +5,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 import util
@@ -42,6 +43,41 @@ def test_dry_run_switch_lets_n_ranks_share_one_gpu(monkeypatch):
     monkeypatch.delenv("M3T_BENCH_SHARE_ONE_GPU")
     with pytest.raises(SystemExit):
         bench.launch_ranks(2, ["--gpus", "2"], n_visible=1)
+
+
+def test_dump_outputs_are_npy_files_within_the_limit(tmp_path):
+    """--dump-outputs: one DIR/<name>.npy per array, float32 / float64 only, a run whose outputs exceed the limit
+    fails instead of writing part of them"""
+    poses = np.arange(2 * 16, dtype=np.float32).reshape(2, 4, 4)
+    bench.write_outputs(str(tmp_path / "out"), {"body2world_poses": poses})
+    got = np.load(str(tmp_path / "out" / "body2world_poses.npy"))
+    assert got.dtype == np.float32 and np.array_equal(got, poses)
+    with pytest.raises(SystemExit):
+        bench.write_outputs(str(tmp_path / "big"), {"x": np.zeros((1 << 17) + 1, np.float64)}, limit_bytes=1 << 20)
+    assert not os.path.exists(str(tmp_path / "big"))
+    with pytest.raises(AssertionError):
+        bench.write_outputs(str(tmp_path / "ints"), {"x": np.zeros(4, np.int32)})
+
+
+def test_long_runs_walk_back_and_forth_over_the_staged_frames():
+    """a run of more steps than bench.MAX_FRAMES stages that many frames: step k looks at frame k while there is one
+    (a run of the default length is what it was), then the steps walk back and forth over frames 1 .. n - 1, every
+    step one frame away from the last; the host-side sequence holds the same frames and ground truth in that order"""
+    seq = [bench.frame_of_step(k, 6) for k in range(20)]
+    assert seq == [0, 1, 2, 3, 4, 5, 4, 3, 2, 1, 2, 3, 4, 5, 4, 3, 2, 1, 2, 3]
+    assert [bench.frame_of_step(k, bench.MAX_FRAMES) for k in range(20 + 5 + 1)] == list(range(26))
+    seq = [bench.frame_of_step(k, bench.MAX_FRAMES) for k in range(1, 10000)]
+    assert all(abs(a - b) == 1 for a, b in zip(seq, seq[1:])) and set(seq) == set(range(1, bench.MAX_FRAMES))
+
+    class Staged:
+        pass
+    staged = Staged()
+    staged.n_frames, staged.gt, staged.color, staged.depth = 4, [[10, 11, 12, 13]], [["a", "b", "c", "d"]], [[None] * 4]
+    walked = bench.walk_frames(staged, 8)
+    assert walked.n_frames == 8 and walked.gt == [[10, 11, 12, 13, 12, 11, 12, 13]]
+    assert walked.color == [["a", "b", "c", "d", "c", "b", "c", "d"]] and walked.depth == [[None] * 8]
+    assert staged.n_frames == 4 and staged.gt == [[10, 11, 12, 13]]  # (the staged inputs are left as they are)
+    assert bench.walk_frames(staged, 3) is staged
 
 
 def test_world_size_must_match_gpus():

@@ -37,7 +37,7 @@ if has tests; then
   (cd tests && timeout 1500 python -m pytest -m gpu -q --timeout=900 2>&1 | grep -vE "^(RCCL|HIP|ROCm|Hostname|Librccl)" | tail -8) > "$OUT/gpu_tests.log" 2>&1
   tail -2 "$OUT/gpu_tests.log"
 fi
-PROF="--steps 10 --warmup 2 --no-cpu-baseline --no-pcie --no-buckets --repeats 1"
+PROF="--full --steps 10 --warmup 2 --no-cpu-baseline --no-pcie --no-buckets --repeats 1"
 if has cal; then  # what FETCH_SIZE / WRITE_SIZE report for known byte counts in the tracking kernels' access patterns
   mkdir -p "$OUT/cal" tools/bin
   [ -x tools/bin/ubench_counters ] || hipcc --offload-arch=gfx950 -O3 -o tools/bin/ubench_counters tools/ubench_counters.hip > "$OUT/cal/build.log" 2>&1
@@ -75,15 +75,15 @@ if has bench; then
   for c in $CONFIGS; do
     extra=""
     [ "$c" = rbot4096 ] && extra="--no-pcie --cpu-seconds 4 --no-cpu-parallel"
-    (timeout 900 python bench.py $(args_of $c) $extra > "$OUT/bench_$c.json" 2> "$OUT/bench_$c.err")
+    (timeout 900 python bench.py --full $(args_of $c) $extra > "$OUT/bench_$c.json" 2> "$OUT/bench_$c.err")
     head -c 400 "$OUT/bench_$c.json"; echo
   done
   # (round 6) the 4096-object line again with the kernel that gathers its pairs from L2: the LDS table's before / after
-  (M3T_HIP_COMPACT_TABLE=0 timeout 900 python bench.py --config rbot64 --objects 4096 --no-pcie --no-cpu-baseline --no-buckets > "$OUT/bench_rbot4096_plain_kernel.json" 2> "$OUT/bench_rbot4096_plain_kernel.err")
+  (M3T_HIP_COMPACT_TABLE=0 timeout 900 python bench.py --full --config rbot64 --objects 4096 --no-pcie --no-cpu-baseline --no-buckets > "$OUT/bench_rbot4096_plain_kernel.json" 2> "$OUT/bench_rbot4096_plain_kernel.err")
   head -c 300 "$OUT/bench_rbot4096_plain_kernel.json"; echo
 fi
 if has extras; then
-  (timeout 900 python bench.py --extras --no-pcie --no-cpu-baseline --no-buckets --busy-seconds 1 > "$OUT/bench_extras.json" 2> "$OUT/bench_extras.err")
+  (timeout 900 python bench.py --full --extras --no-pcie --no-cpu-baseline --no-buckets --busy-seconds 1 > "$OUT/bench_extras.json" 2> "$OUT/bench_extras.err")
   python - "$OUT/bench_extras.json" <<'PY'
 import json, sys
 print(json.dumps(json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]).get("extras"))[:600])
@@ -107,7 +107,7 @@ if has phases; then
 fi
 if has rankshare; then  # what one GPU can say about N: rank 0's share at N = 1, 2, 4, 8 ranks, alone on this GPU (a projection)
   for c in ${RANKSHARE_CONFIGS:-rbot64 synth512 ycb21 chain8}; do
-    (timeout 900 python bench.py --config $c --rank-share 1,2,4,8 --no-cpu-baseline --no-pcie --no-buckets --busy-seconds 1 > "$OUT/rank_share_$c.json" 2> "$OUT/rank_share_$c.err")
+    (timeout 900 python bench.py --full --config $c --rank-share 1,2,4,8 --no-cpu-baseline --no-pcie --no-buckets --busy-seconds 1 > "$OUT/rank_share_$c.json" 2> "$OUT/rank_share_$c.err")
     python - "$OUT/rank_share_$c.json" <<'PY'
 import json, sys
 try:
@@ -130,9 +130,9 @@ if has render; then  # the renderer-fed step of the reference's test scene, 64 t
   done
 fi
 if has sweep; then
-  (timeout 1200 python bench.py --no-pcie --no-cpu-baseline --no-buckets --repeats 3 --sweep 1,8,32,256,512,1024,4096 > "$OUT/bench_sweep.json" 2> "$OUT/bench_sweep.err")
+  (timeout 1200 python bench.py --full --no-pcie --no-cpu-baseline --no-buckets --repeats 3 --sweep 1,8,32,256,512,1024,4096 > "$OUT/bench_sweep.json" 2> "$OUT/bench_sweep.err")
   # SURVEY 8(d) also names 32768 objects (shared cameras above 4096: batch_point): its own run and time limit
-  (timeout 700 python bench.py --no-pcie --no-cpu-baseline --no-buckets --repeats 1 --busy-seconds 1 --sweep 32768 > "$OUT/bench_sweep_32768.json" 2> "$OUT/bench_sweep_32768.err")
+  (timeout 700 python bench.py --full --no-pcie --no-cpu-baseline --no-buckets --repeats 1 --busy-seconds 1 --sweep 32768 > "$OUT/bench_sweep_32768.json" 2> "$OUT/bench_sweep_32768.err")
   python - "$OUT/bench_sweep.json" <<'PY'
 import json, sys
 import os
