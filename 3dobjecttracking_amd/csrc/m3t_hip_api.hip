@@ -277,10 +277,13 @@ struct m3t_hip_context {
   int n_roi_items = 0;
   long long roi_pulls = 0;         // batch-frames uploaded as rectangles so far
   long long roi_repeated = 0;      // bodies whose step was repeated on whole frames so far (read with roi_get_status)
-  DevMem d_search_poses, d_roi_items, d_roi_item_first, d_roi_cam_ids, d_roi_all_cam_ids, d_roi_rects, d_roi_pose_snapshot,
+  DevMem d_search_poses, d_roi_items, d_roi_item_first, d_roi_all_cam_ids, d_roi_rects, d_roi_pose_snapshot,
          d_roi_motion_peak,  // [reader]: adaptive margins (roi_rect_kernel)
          d_roi_opt_of_region;  // [region modality]: its optimizer's row (region_histogram_kernel behind a guarded step)
-  std::vector<int> roi_cam_ids;    // what d_roi_cam_ids holds (a batch whose ids are not consecutive)
+  // the camera lists of the batches whose ids are not consecutive (the colour and the depth cameras of Region + Depth
+  // objects: two lists), each in device memory of its own -- a slot's repair sources point into them
+  static constexpr size_t kRoiScatteredLists = 8;
+  std::vector<std::pair<std::vector<int>, std::unique_ptr<DevMem>>> roi_cam_id_lists;
   int roi_rect_slots = 0;          // d_roi_rects: [slot][camera id]
   // Where the whole frames behind the rectangles of a slot are (the repair after a guarded step reads them): one entry
   // per batch upload into the slot, replaced by the next upload of the same cameras.  The host block has to stay what
@@ -2373,15 +2376,27 @@ int m3t_hip_cameras_upload_batch_roi_async(m3t_hip_context* ctx, const int* ids,
   for (int i = 0; i < n; ++i) consecutive = consecutive && ids[i] == ids[0] + i;
   const int* d_ids = ctx->d_roi_all_cam_ids.as<int>() + ids[0];
   if (!consecutive) {
-    if (ctx->roi_cam_ids != std::vector<int>(ids, ids + n)) {  // (rare: a scattered batch whose camera list changed)
-      HIPCHK(hipStreamSynchronize(ctx->copy_stream[cs]));
-      HIPCHK(hipStreamSynchronize(ctx->stream));  // (a repair may still read the old list)
-      for (auto& sources : ctx->roi_sources) sources.clear();
-      ctx->roi_cam_ids.assign(ids, ids + n);
-      HIPCHK(ctx->d_roi_cam_ids.alloc(size_t(n) * sizeof(int)));
-      HIPCHK(hipMemcpy(ctx->d_roi_cam_ids.p, ids, size_t(n) * sizeof(int), hipMemcpyHostToDevice));
+    // Every scattered batch keeps its own list.  (Until now there was one list for all of them: the depth cameras' batch
+    // replaced the colour cameras' list and cleared every slot's repair sources, so a body of Region + Depth objects
+    // that left its rectangle was repeated without its colour frame and stayed uncommitted.)
+    const std::vector<int> wanted(ids, ids + n);
+    const DevMem* list = nullptr;
+    for (auto& l : ctx->roi_cam_id_lists)
+      if (l.first == wanted) list = l.second.get();
+    if (!list) {
+      if (ctx->roi_cam_id_lists.size() >= Ctx::kRoiScatteredLists) {  // (rare: camera lists that keep changing)
+        HIPCHK(hipStreamSynchronize(ctx->copy_stream[cs]));
+        HIPCHK(hipStreamSynchronize(ctx->stream));  // (a repair may still read an old list)
+        for (auto& sources : ctx->roi_sources) sources.clear();
+        ctx->roi_cam_id_lists.clear();
+      }
+      auto mem = std::make_unique<DevMem>();
+      HIPCHK(mem->alloc(size_t(n) * sizeof(int)));
+      HIPCHK(hipMemcpy(mem->p, ids, size_t(n) * sizeof(int), hipMemcpyHostToDevice));
+      list = mem.get();
+      ctx->roi_cam_id_lists.emplace_back(wanted, std::move(mem));
     }
-    d_ids = ctx->d_roi_cam_ids.as<int>();
+    d_ids = list->as<int>();
   }
   long last_read = -1;
   for (int i = 0; i < n; ++i) last_read = std::max(last_read, ctx->cameras[ids[i]]->last_read_step[slot]);
@@ -3640,17 +3655,33 @@ int m3t_hip_set_object_split(m3t_hip_context* ctx, int enable) {
   return M3T_OK;
 }
 
+// The sub-steps outside the fused step (start_modalities, calculate_correspondences, calculate_results) read the
+// modalities' current frames unguarded: outside the trackers' rectangle a slot filled by ROI ingest holds whatever an
+// earlier frame left there -- and a body reset between two steps reads its histogram pixels around the new pose, away
+// from the rectangle of the old one.  Refused; the caller uploads the whole frame into the slot first (m3t_hip.h).
+static int RequireWholeFrames(Ctx* ctx, const char* entry) {
+  auto roi = [ctx](int c) { return c >= 0 && ctx->cameras[c]->slot_is_roi[ctx->cameras[c]->current]; };
+  bool roi_frames = false;
+  for (auto& m : ctx->region_mods) roi_frames = roi_frames || roi(m->camera) || roi(m->depth_camera);
+  for (auto& m : ctx->depth_mods) roi_frames = roi_frames || roi(m->camera);
+  REQUIRE(!roi_frames, M3T_ERR_UNSUPPORTED,
+          std::string(entry) + ": a frame slot the modalities read holds the trackers' rectangle only (ROI ingest); "
+          "upload the whole frame into it first (camera_upload_slot)");
+  return M3T_OK;
+}
+
 int m3t_hip_start_modalities(m3t_hip_context* ctx, int iteration) {
   CHECK_CTX();
   HIPCHK(hipSetDevice(ctx->device));
+  int r = RequireWholeFrames(ctx, "start_modalities");
+  if (r) return r;
   for (auto& m : ctx->region_mods) {  // RegionModality::StartModality :378
     if (m->dev.first_iteration != iteration) {
       m->dev.first_iteration = iteration;
       ctx->tables_dirty = true;
     }
   }
-  int r = Prepare(ctx, true);
-  if (r) return r;
+  if ((r = Prepare(ctx, true))) return r;
   if (ctx->table_overflow_host) {  // new histograms: the LDS pair table gets its chance again
     HIPCHK(hipStreamSynchronize(ctx->stream));
     *static_cast<volatile unsigned*>(ctx->table_overflow_host) = 0u;
@@ -3661,7 +3692,9 @@ int m3t_hip_start_modalities(m3t_hip_context* ctx, int iteration) {
 int m3t_hip_calculate_correspondences(m3t_hip_context* ctx, int iteration, int corr_iteration) {
   CHECK_CTX();
   HIPCHK(hipSetDevice(ctx->device));
-  int r = Prepare(ctx, true);
+  int r = RequireWholeFrames(ctx, "calculate_correspondences");
+  if (r) return r;
+  r = Prepare(ctx, true);
   if (r) return r;
   ctx->state_valid = true;
   if ((r = RenderForModalities(ctx, false))) return r;  // correspondence_renderer_ptrs tracker.cpp:447-452
@@ -3791,7 +3824,9 @@ int m3t_hip_calculate_consistent_poses(m3t_hip_context* ctx) {
 int m3t_hip_calculate_results(m3t_hip_context* ctx, int iteration) {
   CHECK_CTX();
   HIPCHK(hipSetDevice(ctx->device));
-  int r = Prepare(ctx, true);
+  int r = RequireWholeFrames(ctx, "calculate_results");
+  if (r) return r;
+  r = Prepare(ctx, true);
   if (r) return r;
   if ((r = RenderForModalities(ctx, true))) return r;  // results_renderer_ptrs tracker.cpp:503-509
   return LaunchHistogram(ctx, iteration, false);

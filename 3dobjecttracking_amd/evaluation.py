@@ -57,7 +57,9 @@ def evaluate_rbot_sequence(tracker, body, poses_gt, load_image, n_frames=None, r
         body.set_body2world_pose(poses_gt[i])
         for r in reset_renderers:
             r.StartRendering()
-        tracker.StartModalities(0)
+        # (refused, e.g., while a frame slot holds an ROI rectangle only: the loop must not go on with stale histograms)
+        if not tracker.StartModalities(0):
+            raise RuntimeError("StartModalities failed")
 
     load_image(0)
     reset(0)

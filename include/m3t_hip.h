@@ -151,7 +151,11 @@ int m3t_hip_camera_slot_sync(m3t_hip_context*, int camera_id, int slot);
  * results bit for bit either way.  roi_get_status returns (and clears) the bodies that were repeated since the last
  * call -- a count of how often the margin was too small; roi_get_unrecovered the ones whose repeat could not see a
  * whole frame either (the host block of the slot was not known any more, e.g. tables rebuilt in between): their step
- * is still uncommitted -- upload the frame in full and execute the step again. */
+ * is still uncommitted -- upload the frame in full and execute the step again.
+ * Only execute_tracking_step reads a slot that holds a rectangle.  start_modalities, calculate_correspondences and
+ * calculate_results (and refine_poses, which calls them) return M3T_ERR_UNSUPPORTED while a current slot of a camera
+ * the modalities read holds one: outside the rectangle it holds what an earlier frame left.  An evaluator that resets
+ * a body and restarts the modalities uploads the whole current frame into that slot first (camera_upload_slot). */
 int m3t_hip_set_roi_ingest(m3t_hip_context*, int enable, float margin_px);
 int m3t_hip_cameras_upload_batch_roi_async(m3t_hip_context*, const int* camera_ids, int n_cameras, int slot, const void* base,
                                            size_t camera_stride, size_t row_step);

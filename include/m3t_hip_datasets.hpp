@@ -122,7 +122,8 @@ inline std::vector<RunResult> EvaluateRbotDataset(
       };
       auto reset = [&](int k) {  // ResetBody rbot_evaluator.cpp:334-342
         body.set_body2world_pose(poses[size_t(k)]);
-        tracker.StartModalities(0);
+        // (refused, e.g., while a frame slot holds an ROI rectangle only: the loop must not go on with stale histograms)
+        if (!tracker.StartModalities(0)) throw std::runtime_error("StartModalities failed");
       };
       RunResult r;
       r.sequence = sequence;

@@ -2,6 +2,8 @@
 ragged and empty line sets, objects leaving the image or behind the camera, adaptive coverage,
 non-default distribution / function lengths, every template and the generic pixel-walk path,
 heterogeneous parameters inside one batch, several bodies sharing one camera (YCB shape)."""
+import ctypes as C
+
 import numpy as np
 import pytest
 
@@ -123,13 +125,55 @@ def test_heterogeneous_batch():
         for x, y in ((a1, b1), (a2, b2)):
             for ra, rb in zip(x.region, y.region):
                 _assert_lines_equal(ra.data_lines(), rb.data_lines())
-    # fused step over the mixed batch stays within one-step tolerance
+    # fused step over the mixed batch: every pose equals the oracle's
     hip.call("set_fused_step", 1)
     for x, y in ((a1, b1), (a2, b2)):
         x.set_poses(y.poses())
     assert a1.tracker.ExecuteTrackingStep(0) and b1.tracker.ExecuteTrackingStep(0)
-    st = [syn.pose_errors(p, q) for x, y in ((a1, b1), (a2, b2)) for p, q in zip(x.poses(), y.poses())]
-    assert np.median([e[0] for e in st]) < 1e-5 and np.median([e[1] for e in st]) < 1e-6
+    for x, y in ((a1, b1), (a2, b2)):
+        assert np.array_equal(np.stack(x.poses()), np.stack(y.poses()))
+
+
+@pytest.mark.parametrize("env,kind", [({}, "split"), ({"M3T_HIP_NO_SPLIT": "1"}, "one workgroup"),
+                                      ({"M3T_HIP_NO_SPLIT": "1", "M3T_HIP_COMPACT": "1"}, "compact")])
+def test_heterogeneous_batch_free_running(env, kind, monkeypatch):
+    """the mixed batch of test_heterogeneous_batch (32 and 8 bins, other scales and image sizes, function_slope)
+    free running over four frames through every fused launch shape: poses after every frame and histograms equal the
+    oracle's"""
+    for k in ("M3T_HIP_NO_SPLIT", "M3T_HIP_SPLIT_PARTS", "M3T_HIP_THREADS", "M3T_HIP_COMPACT", "M3T_HIP_COMPACT_TABLE"):
+        monkeypatch.delenv(k, raising=False)
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    inputs_a = scenes.Inputs(2, 4, n_divides=2)
+    inputs_b = scenes.Inputs(2, 4, n_divides=1, intr=dict(syn.RBOT_INTRINSICS, width=480, height=360, ppu=240, ppv=180),
+                             first_object=7)
+    out = []
+    for api in (util.open_hip(), util.open_oracle()):
+        i1 = scenes.Instance(api, inputs_a)
+        i2 = scenes.Instance(api, inputs_b, region_params=dict(
+            syn.RBOT_REGION_PARAMS, n_lines_max=90, n_histogram_bins=8, scales=[4, 2, 1],
+            standard_deviations=[15.0, 5.0, 1.5], function_slope=0.5, function_amplitude=0.43))
+        for inst in (i1, i2):
+            inst.upload_frame(0)
+        assert i1.tracker.StartModalities(0)
+        poses = []
+        for k in range(inputs_a.n_frames):
+            for inst in (i1, i2):
+                inst.upload_frame(k)
+            assert i1.tracker.ExecuteTrackingStep(k)
+            poses.append(np.stack(i1.poses() + i2.poses()))
+        if not out:  # the device context
+            name = C.create_string_buffer(64)
+            api.call("get_step_kernel", name, 64)
+            kernel = name.value.decode()
+        out.append((poses, [r.histograms() for r in i1.region + i2.region]))
+    (pa, ha), (pb, hb) = out
+    for k, (x, y) in enumerate(zip(pa, pb)):
+        assert np.array_equal(x, y), k
+    for (fa, ba), (fb, bb) in zip(ha, hb):
+        assert np.array_equal(fa, fb) and np.array_equal(ba, bb)
+    assert kernel.startswith("tracking_step_") and ("split" in kernel) == (kind == "split") and \
+        ("compact" in kernel) == (kind == "compact"), kernel
 
 
 def test_bodies_sharing_one_camera():

@@ -167,8 +167,8 @@ def test_closed_chain_over_thread_ranks_equals_one_context(world, soft):
     """the _constrained_ twin of the segment kernel with partial ownership: the closed three-body loop (constraint rows
     in the system / soft-constraint terms onto the link sums AFTER the reduction: counted once) held by 2 and 3
     contexts.  Same device arithmetic as one context that owns everything and takes the one-launch constrained kernel:
-    compared bit for bit (against the oracle the constrained structures carry the atan2f / tan tolerance of
-    test_closed_chain_with_a_hard_constraint_matches_the_oracle, so the single context is the yardstick here)"""
+    compared bit for bit (test_closed_chain_with_a_hard_constraint_matches_the_oracle compares that single context with
+    the oracle, array_equal, so the single context is the yardstick here)"""
     inputs = scenes.Inputs(3, 1, n_divides=2)
     rng = np.random.default_rng(3)
     j1 = syn.make_pose(syn.rot_vec([0.2, -0.1, 0.3]), [0.05, 0.01, 0.0])
