@@ -1,7 +1,12 @@
 """Edge cases of the path, HIP vs oracle (bit-exact per-line state / histograms unless noted):
 ragged and empty line sets, objects leaving the image or behind the camera, adaptive coverage,
 non-default distribution / function lengths, every template and the generic pixel-walk path,
-heterogeneous parameters inside one batch, several bodies sharing one camera (YCB shape)."""
+heterogeneous parameters inside one batch, several bodies sharing one camera (YCB shape).
+
+The first four tests (test_every_scale_variant, test_function_and_distribution_lengths, test_ragged_and_empty_line_sets,
+test_fewer_model_points_than_lines_and_adaptive_coverage) switch the fused step off and drive the UNFUSED sub-step kernels
+one call at a time: that is what gives them the per-line state after every sub-step.  The same edges through the fused
+step kernels -- one launch per frame, what bench.py times -- are in tests/test_gpu_fused_edges.py."""
 import ctypes as C
 
 import numpy as np
