@@ -323,6 +323,7 @@ _HIP_ONLY = {
     "get_step_kernel": [C.c_char_p, C.c_size_t],
     "debug_log_checksum": [C.c_uint, C.c_uint, C.POINTER(C.c_ulonglong)],
     "set_object_split": [C.c_int],
+    "reset_bodies": [c_int_p, c_float_p, C.c_int, C.c_int],
 }
 
 

@@ -322,6 +322,12 @@ struct m3t_hip_context {
   size_t cam_stage_bytes = 0;
   hipEvent_t cam_stage_done[kStage] = {nullptr};
   int cam_stage_next = 0;
+  // m3t_hip_reset_bodies: the call's lists and poses, in mapped host memory the two launches read in place
+  static constexpr int kResetStage = 4;
+  void* reset_stage[kResetStage] = {nullptr};
+  size_t reset_stage_bytes[kResetStage] = {0};
+  hipEvent_t reset_stage_done[kResetStage] = {nullptr};
+  int reset_stage_next = 0;
   // asynchronous ingest: frame copies run on their own stream beside the tracking kernels
   static constexpr int kStepEvents = 16;
   static constexpr int kCopyStreams = 4;  // cameras are spread round-robin: per-copy DMA latencies overlap
@@ -1541,6 +1547,8 @@ int UploadTables(Ctx* ctx) {
                                hipFuncAttributeMaxDynamicSharedMemorySize, int(ctx->lds_corr)));
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(region_histogram_kernel),
                                hipFuncAttributeMaxDynamicSharedMemorySize, int(ctx->lds_hist)));
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(region_histogram_list_kernel),
+                               hipFuncAttributeMaxDynamicSharedMemorySize, int(ctx->lds_hist)));
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(depth_correspondence_kernel),
                                hipFuncAttributeMaxDynamicSharedMemorySize, int(ctx->lds_depth)));
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(depth_gradient_hessian_kernel),
@@ -1903,6 +1911,10 @@ void m3t_hip_destroy(m3t_hip_context* ctx) {
   for (int i = 0; i < m3t_hip_context::kStage; ++i) {
     if (ctx->cam_stage[i]) (void)hipHostFree(ctx->cam_stage[i]);
     if (ctx->cam_stage_done[i]) (void)hipEventDestroy(ctx->cam_stage_done[i]);
+  }
+  for (int i = 0; i < m3t_hip_context::kResetStage; ++i) {
+    if (ctx->reset_stage[i]) (void)hipHostFree(ctx->reset_stage[i]);
+    if (ctx->reset_stage_done[i]) (void)hipEventDestroy(ctx->reset_stage_done[i]);
   }
   for (auto& c : ctx->cameras)
     for (auto& e : c->slot_copied)
@@ -3688,6 +3700,114 @@ int m3t_hip_start_modalities(m3t_hip_context* ctx, int iteration) {
   }
   if ((r = RenderForModalities(ctx, true))) return r;  // start_modality_renderer_ptrs tracker.cpp:430-436
   return LaunchHistogram(ctx, iteration, true);
+}
+// RBOTEvaluator::ResetBody (rbot_evaluator.cpp:334-342) for n bodies of the batch: their poses, the start-modality
+// renderers their modalities read, StartModality of their region modalities -- enqueued behind whatever the stream
+// holds, without reading poses back, waiting for the stream or uploading a table again (m3t_hip.h).
+int m3t_hip_reset_bodies(m3t_hip_context* ctx, const int* body_ids, const float* body2world_poses, int n, int iteration) {
+  CHECK_CTX();
+  REQUIRE(n >= 0, M3T_ERR_INVALID_ARGUMENT, "reset_bodies: n must not be negative");
+  if (n == 0) return M3T_OK;
+  REQUIRE(body_ids, M3T_ERR_INVALID_ARGUMENT, "reset_bodies: null body ids");
+  const int n_all = int(ctx->body_poses.size() / 16);
+  std::vector<char> listed(size_t(n_all), 0);
+  for (int i = 0; i < n; ++i) {
+    REQUIRE(body_ids[i] >= 0 && body_ids[i] < n_all, M3T_ERR_INVALID_ARGUMENT, "reset_bodies: bad body id");
+    REQUIRE(!listed[body_ids[i]], M3T_ERR_INVALID_ARGUMENT, "reset_bodies: a body id is listed twice");
+    listed[body_ids[i]] = 1;
+  }
+  for (auto& l : ctx->links)
+    REQUIRE(l.body < 0 || !listed[l.body] || (l.parent < 0 && l.children.empty()), M3T_ERR_UNSUPPORTED,
+            "reset_bodies: a listed body belongs to a structure of more than one link (set the poses of the "
+            "structure and call start_modalities)");
+  std::vector<int> region_ids, renderer_ids, cameras;
+  for (size_t i = 0; i < ctx->region_mods.size(); ++i) {
+    const RegionMod& m = *ctx->region_mods[i];
+    if (!listed[m.body]) continue;
+    REQUIRE(m.shared_histograms < 0, M3T_ERR_UNSUPPORTED,
+            "reset_bodies: a region modality of a listed body uses shared ColorHistograms (call start_modalities)");
+    region_ids.push_back(int(i));
+    cameras.push_back(m.camera);
+    if (m.depth_camera >= 0) cameras.push_back(m.depth_camera);
+    for (int renderer : {m.dev.model_occlusions ? m.depth_renderer : -1, m.dev.use_region_checking ? m.silhouette_renderer : -1})
+      if (renderer >= 0 && std::find(renderer_ids.begin(), renderer_ids.end(), renderer) == renderer_ids.end())
+        renderer_ids.push_back(renderer);
+  }
+  for (auto& m : ctx->depth_mods)
+    if (listed[m->body]) cameras.push_back(m->camera);
+  for (int c : cameras)  // (the same refusal as RequireWholeFrames, for the cameras these bodies' modalities read)
+    REQUIRE(!ctx->cameras[c]->slot_is_roi[ctx->cameras[c]->current], M3T_ERR_UNSUPPORTED,
+            "reset_bodies: a frame slot the modalities read holds the trackers' rectangle only (ROI ingest); "
+            "upload the whole frame into it first (camera_upload_slot)");
+  HIPCHK(hipSetDevice(ctx->device));
+  const bool untracked_before = ctx->untracked_launches;
+  if (ctx->poses_dirty_host) ctx->roi_end_valid = false;  // poses set by the host: the last step's end no longer vouches for them
+  int r = Prepare(ctx, true);  // (tables and poses that were waiting for their upload anyway)
+  if (r) return r;
+  ctx->untracked_launches = untracked_before;  // tracked by a step_done event below
+  // the call's arguments: [body ids][region modality ids][renderer ids][{renderer, -1} pairs][poses]
+  const size_t n_region = region_ids.size(), n_render = renderer_ids.size();
+  const size_t ints = size_t(n) + n_region + 3 * n_render;
+  const size_t off_poses = (ints * 4 + 15) / 16 * 16;
+  const size_t bytes = off_poses + (body2world_poses ? size_t(n) * 64 : 0);
+  const int stage = ctx->reset_stage_next;
+  ctx->reset_stage_next = (stage + 1) % Ctx::kResetStage;
+  if (!ctx->reset_stage_done[stage]) HIPCHK(hipEventCreateWithFlags(&ctx->reset_stage_done[stage], hipEventDisableTiming));
+  HIPCHK(hipEventSynchronize(ctx->reset_stage_done[stage]));  // the call four resets ago: normally long complete
+  if (ctx->reset_stage_bytes[stage] < bytes) {
+    if (ctx->reset_stage[stage]) HIPCHK(hipHostFree(ctx->reset_stage[stage]));
+    ctx->reset_stage[stage] = nullptr;
+    ctx->reset_stage_bytes[stage] = 0;
+    HIPCHK(hipHostMalloc(&ctx->reset_stage[stage], bytes * 2, hipHostMallocMapped));
+    ctx->reset_stage_bytes[stage] = bytes * 2;
+  }
+  int* h_ints = static_cast<int*>(ctx->reset_stage[stage]);
+  std::memcpy(h_ints, body_ids, size_t(n) * 4);
+  if (n_region) std::memcpy(h_ints + n, region_ids.data(), n_region * 4);
+  for (size_t k = 0; k < n_render; ++k) {
+    h_ints[size_t(n) + n_region + k] = renderer_ids[k];
+    h_ints[size_t(n) + n_region + n_render + 2 * k] = renderer_ids[k];
+    h_ints[size_t(n) + n_region + n_render + 2 * k + 1] = -1;
+  }
+  if (body2world_poses) std::memcpy(static_cast<uint8_t*>(ctx->reset_stage[stage]) + off_poses, body2world_poses, size_t(n) * 64);
+  void* dev = nullptr;
+  HIPCHK(hipHostGetDevicePointer(&dev, ctx->reset_stage[stage], 0));
+  const int* d_ints = static_cast<const int*>(dev);
+  const float* d_new_poses = body2world_poses ? reinterpret_cast<const float*>(static_cast<const uint8_t*>(dev) + off_poses) : nullptr;
+  const int items = std::max(body2world_poses ? n * 16 : 0, int(n_region));
+  if (items > 0)
+    hipLaunchKernelGGL(reset_bodies_scatter_kernel, dim3((items + 255) / 256), dim3(256), 0, ctx->stream,
+                       ctx->d_poses.as<float>(), d_ints, d_new_poses, n, ctx->d_region.as<RegionModDev>(), d_ints + n,
+                       int(n_region), iteration);
+  // the host mirrors follow (the poses' only where the host copy counts: the device stays authoritative)
+  if (body2world_poses) {
+    for (int i = 0; i < n; ++i) std::memcpy(&ctx->body_poses[size_t(body_ids[i]) * 16], body2world_poses + size_t(i) * 16, 64);
+    ctx->roi_end_valid = false;  // the next step's rectangles start from a snapshot of these poses
+  }
+  for (int id : region_ids) ctx->region_mods[id]->dev.first_iteration = iteration;
+  if (n_render) {
+    int largest = 0;
+    for (int id : renderer_ids) {
+      ctx->renderers[id]->rendered = true;
+      largest = std::max(largest, ctx->renderers[id]->image_size);
+    }
+    if ((r = LaunchRenderers(ctx, d_ints + n + n_region, int(n_render), d_ints + n + n_region + n_render, int(n_render), largest)))
+      return r;
+  }
+  if (n_region) {
+    ScopedKernelTimer timer(ctx, 1);
+    hipLaunchKernelGGL(region_histogram_list_kernel, dim3(unsigned(n_region)), dim3(M3T_BLOCK_THREADS), ctx->lds_hist,
+                       ctx->stream, ctx->d_region.as<RegionModDev>(), d_ints + n, ctx->cams_active,
+                       ctx->d_poses.as<float>(), ctx->hist_counts_in_lds ? 1 : 0);
+  }
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(ctx->reset_stage_done[stage], ctx->stream));
+  if (ctx->async_ingest) {  // a later asynchronous upload into a slot these launches read waits for them
+    HIPCHK(hipEventRecord(ctx->step_done[ctx->step_counter % Ctx::kStepEvents], ctx->stream));
+    for (int c : cameras) ctx->cameras[c]->last_read_step[ctx->cameras[c]->current] = ctx->step_counter;
+    ++ctx->step_counter;
+  }
+  return M3T_OK;
 }
 int m3t_hip_calculate_correspondences(m3t_hip_context* ctx, int iteration, int corr_iteration) {
   CHECK_CTX();

@@ -2864,6 +2864,42 @@ region_histogram_kernel(const RegionModDev* mods, const CameraDev* cams, const f
   }
 }
 
+// m3t_hip_reset_bodies, first launch: the listed bodies take their new poses (poses == nullptr: they keep them) and the
+// listed region modalities their first_iteration (RegionModality::StartModality :378) -- the few words of the pose
+// and modality tables a reset changes, written in place; nothing else of either table is touched.
+__global__ void __launch_bounds__(256)
+reset_bodies_scatter_kernel(float* body_poses, const int* body_ids, const float* poses, int n_bodies,
+                            RegionModDev* mods, const int* region_ids, int n_region, int iteration) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (poses && i < n_bodies * 16) body_poses[16 * body_ids[i >> 4] + (i & 15)] = poses[i];
+  if (i < n_region) mods[region_ids[i]].first_iteration = iteration;
+}
+
+// m3t_hip_reset_bodies, second launch: StartModality (:375-388) of the region modalities region_ids[0 .. gridDim.x), one
+// workgroup each -- region_histogram_kernel's initialize branch driven by a list (own histograms only: the entry
+// point refuses shared ColorHistograms).
+__global__ void __launch_bounds__(M3T_BLOCK_THREADS)
+region_histogram_list_kernel(const RegionModDev* mods, const int* region_ids, const CameraDev* cams,
+                             const float* body_poses, int counts_in_lds) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  CRegion& m = *(CRegion*)(mods + region_ids[blockIdx.x]);
+  CCam& cam = *(CCam*)(cams + m.camera);
+  CCam* dcam = m.measure_occlusions ? (CCam*)(cams + m.depth_camera) : nullptr;
+  const Affine b2w = load_pose(body_poses + 16 * m.body);
+  const Affine b2c = mul_pose(load_pose(cam.world2camera), b2w);
+  Affine b2dc = b2c;
+  if (dcam) b2dc = mul_pose(load_pose(dcam->world2camera), b2w);
+  const bool handle_occlusions = m.n_unoccluded_iterations == 0;
+  float* misc = lds;
+  if (counts_in_lds) {
+    region_histogram_update(m, cam, dcam, b2c, b2dc, handle_occlusions, true,
+                            (__attribute__((address_space(3))) uint32_t*)(lds + M3T_MISC_FLOATS), misc);
+  } else {
+    region_histogram_update(m, cam, dcam, b2c, b2dc, handle_occlusions, true,
+                            (__attribute__((address_space(1))) uint32_t*)m.count_scratch, misc);
+  }
+}
+
 // one workgroup per shared ColorHistograms object, after every modality has added its samples
 __global__ void __launch_bounds__(M3T_BLOCK_THREADS)
 shared_histogram_finish_kernel(const SharedHistogramsDev* shared, int initialize) {

@@ -81,6 +81,40 @@ def evaluate_rbot_sequence(tracker, body, poses_gt, load_image, n_frames=None, r
     return frames, avg
 
 
+def evaluate_rbot_sequences(tracker, bodies, poses_gt_per_body, load_images, n_frames):
+    """The loop of evaluate_rbot_sequence for N independent bodies in ONE context (HIP library): every body starts on
+    image 0 at its own ground truth, cycle i tracks image i + 1 of all of them in one step, every body is judged
+    against its own ground truth, and the lost ones -- those alone -- are reset with one Tracker.ResetBodies call
+    (ResetBody :334-342 per body: its pose, StartModality(0, 0) of its modalities), so that each body's results are
+    those of a tracker of its own.  `load_images(k)` makes image k current in every body's camera.
+    Returns (per-body lists of per-frame results, per-body averages); complete_cycle is the time of the batch's step."""
+    for body, poses_gt in zip(bodies, poses_gt_per_body):
+        body.set_body2world_pose(poses_gt[0])
+    load_images(0)
+    if not tracker.StartModalities(0):
+        raise RuntimeError("StartModalities failed")
+    frames = [[] for _ in bodies]
+    for i in range(n_frames):
+        load_images(i + 1)
+        t0 = time.perf_counter()
+        ok = tracker.ExecuteTrackingStep(i) and tracker.Sync()
+        dt = (time.perf_counter() - t0) * 1e6
+        if not ok:
+            raise RuntimeError("tracking step %d failed" % i)
+        lost = []
+        for j, (body, poses_gt) in enumerate(zip(bodies, poses_gt_per_body)):
+            t_err, r_err, success = rbot_pose_result(body.body2world_pose(), poses_gt[i + 1])
+            frames[j].append(dict(frame_index=i, translation_error=t_err, rotation_error=r_err,
+                                  tracking_success=success, complete_cycle=dt))
+            if success == 0.0:
+                lost.append(j)
+        if lost and not tracker.ResetBodies([bodies[j] for j in lost], [poses_gt_per_body[j][i + 1] for j in lost], 0):
+            raise RuntimeError("ResetBodies failed")
+    keys = ("translation_error", "rotation_error", "tracking_success", "complete_cycle")
+    averages = [{k: float(np.mean([f[k] for f in fs])) for k in keys} for fs in frames]
+    return frames, averages
+
+
 # ---------------------------------------------------------------------------------------------------------
 # YCB-Video
 # ---------------------------------------------------------------------------------------------------------
@@ -227,7 +261,7 @@ def evaluate_rbot_dataset(open_context, dataset_directory, external_directory, b
                           sequence_names=RBOT_SEQUENCE_NAMES, n_frames=1000, region_parameters=None,
                           model_parameters=None, tikhonov_parameter_rotation=1000.0,
                           tikhonov_parameter_translation=30000.0, n_corr_iterations=7, n_update_iterations=2,
-                          report=None, shard=(0, 1)):
+                          report=None, shard=(0, 1), batch=1):
     """RBOTEvaluator::SetUp + Evaluate for the region modality on the un-modelled sequences: for every (sequence,
     body) a tracker on `dataset/<body>/frames/<sequence>NNNN.png`, started at `dataset/poses_first.txt`, reset on
     loss, scored with the 5 cm / 5 degree criterion.  Bodies are `dataset/<body>/<body>.obj` in millimetres
@@ -237,11 +271,19 @@ def evaluate_rbot_dataset(open_context, dataset_directory, external_directory, b
     average (CalculateAverageResult); `report`, if given, is called with each run's title and result.
     shard = (rank, world): this process takes every world-th run (the reference spreads the runs over OpenMP
     threads, rbot_evaluator.cpp:139-156; here one process per GPU takes its share and the caller merges the
-    dictionaries)."""
+    dictionaries).
+    batch > 1 (HIP library): up to `batch` of this process's runs share one context -- each with its own body, model,
+    loader camera and optimizer -- and go through evaluate_rbot_sequences, which resets the lost bodies alone; the
+    results are those of batch = 1."""
     import os
 
     from . import config as cfg
     from . import generator, host
+    if batch > 1:
+        return _evaluate_rbot_dataset_batched(open_context, dataset_directory, external_directory, body_names,
+                                              sequence_names, n_frames, region_parameters, model_parameters,
+                                              tikhonov_parameter_rotation, tikhonov_parameter_translation,
+                                              n_corr_iterations, n_update_iterations, report, shard, batch)
     poses_first = read_poses_rbot(os.path.join(dataset_directory, "poses_first.txt"), n_frames)
     region_parameters = dict(RBOT_REGION_PARAMETERS, **(region_parameters or {}))
     model_parameters = dict(RBOT_MODEL_PARAMETERS, **(model_parameters or {}))
@@ -275,6 +317,60 @@ def evaluate_rbot_dataset(open_context, dataset_directory, external_directory, b
         results[(sequence, name)] = average
         if report is not None:
             report(sequence + "_" + name, average)
+    keys = ("translation_error", "rotation_error", "tracking_success", "complete_cycle")
+    overall = {k: float(np.mean([r[k] for r in results.values()])) for k in keys}
+    return results, overall
+
+
+def _evaluate_rbot_dataset_batched(open_context, dataset_directory, external_directory, body_names, sequence_names,
+                                   n_frames, region_parameters, model_parameters, tikhonov_parameter_rotation,
+                                   tikhonov_parameter_translation, n_corr_iterations, n_update_iterations, report,
+                                   shard, batch):
+    """evaluate_rbot_dataset with up to `batch` runs per context (same runs, same order, same results)"""
+    import os
+
+    from . import config as cfg
+    from . import generator, host
+    poses_first = read_poses_rbot(os.path.join(dataset_directory, "poses_first.txt"), n_frames)
+    region_parameters = dict(RBOT_REGION_PARAMETERS, **(region_parameters or {}))
+    model_parameters = dict(RBOT_MODEL_PARAMETERS, **(model_parameters or {}))
+    results = {}
+    runs = [(sequence, name) for sequence in sequence_names for name in body_names][shard[0]::shard[1]]
+    for first in range(0, len(runs), batch):
+        chunk = runs[first:first + batch]
+        api = open_context()
+        bodies, cameras = [], []
+        for sequence, name in chunk:
+            body = generator.Body(api, name, os.path.join(dataset_directory, name, name + ".obj"), 0.001, True, False,
+                                  np.eye(4, dtype=F))
+            model_path = os.path.join(external_directory, "models", name + "_model.bin")
+            if cfg.model_bin_matches(model_path, True, model_parameters, body.body_data()):
+                model = host.RegionModel(api, path=model_path)
+            else:
+                generation = {k: v for k, v in model_parameters.items() if k != "use_random_seed"}
+                model = host.RegionModel.generate(api, body, **generation)
+                cfg.write_model_bin(model_path, True, model_parameters, body.body_data(), *model.views())
+            camera = generator.LoaderColorCamera(api, os.path.join(dataset_directory, name, "frames"), RBOT_INTRINSICS,
+                                                 sequence, 0, 4)
+            modality = host.RegionModality(api, body, camera, model, **region_parameters)
+            host.Optimizer(api, body=body, modalities=[modality],
+                           tikhonov_parameter_rotation=tikhonov_parameter_rotation,
+                           tikhonov_parameter_translation=tikhonov_parameter_translation)
+            bodies.append(body)
+            cameras.append(camera)
+        tracker = host.Tracker(api, n_corr_iterations, n_update_iterations)
+
+        def load_images(k, cameras=cameras):
+            for camera in cameras:
+                camera.set_load_index(k)
+                if not camera.UpdateImage():
+                    raise RuntimeError("Could not read image from %s" % camera.image_path())
+
+        _, averages = evaluate_rbot_sequences(tracker, bodies, [poses_first] * len(chunk), load_images, n_frames)
+        for (sequence, name), average in zip(chunk, averages):
+            results[(sequence, name)] = average
+            if report is not None:
+                report(sequence + "_" + name, average)
     keys = ("translation_error", "rotation_error", "tracking_success", "complete_cycle")
     overall = {k: float(np.mean([r[k] for r in results.values()])) for k in keys}
     return results, overall

@@ -69,6 +69,20 @@ class Tracker:
     def ExecuteTrackingStep(self, iteration):
         return self._step("execute_tracking_step", iteration)
 
+    def ResetBodies(self, bodies, poses=None, iteration=0):
+        """RBOTEvaluator::ResetBody (rbot_evaluator.cpp:334-352) for `bodies` alone, in one call (HIP library only):
+        their poses (None: the poses stay), the start-modality renderers their modalities read and
+        StartModality(iteration) of their region modalities; every other body keeps its state bit for bit"""
+        ids = np.asarray([b.id for b in bodies], np.int32)
+        flat = None
+        if poses is not None:
+            assert len(poses) == len(ids)
+            flat = np.ascontiguousarray(np.concatenate([pose_arg(p) for p in poses]) if len(ids) else
+                                        np.zeros(0, np.float32), np.float32)
+        if "reset_bodies" not in self.api._fn:
+            raise M3TError(-3, "%sreset_bodies: this entry point exists in the HIP library only" % self.api.prefix)
+        return self._step("reset_bodies", iptr(ids), fptr(flat) if flat is not None else None, len(ids), iteration)
+
     # asynchronous ingest (HIP library only)
     def register_host_buffer(self, array):
         """page-lock a caller-owned frame buffer so that asynchronous uploads overlap the tracking kernels"""

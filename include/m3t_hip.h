@@ -280,6 +280,35 @@ int m3t_hip_link_get_joint_poses(m3t_hip_context*, int link_id, float body2joint
  * Same names, arguments and order as the reference's public Tracker methods. */
 int m3t_hip_tracker_set_iterations(m3t_hip_context*, int n_corr_iterations, int n_update_iterations);
 int m3t_hip_start_modalities(m3t_hip_context*, int iteration);                     /* tracker.cpp:430 */
+/* RBOTEvaluator::ResetBody / ResetOcclusionBody (examples/rbot_evaluator.cpp:334-352) for n bodies of the batch in one
+ * call: what an evaluator of independent sequences does to the bodies it judged lost, and to no other.
+ *   - body2world_poses (n x 16, column-major, or NULL: the poses stay): the listed bodies get these poses exactly as
+ *     body_set_body2world_pose would give them; no other body's pose is touched.
+ *   - the start-modality renderers the listed bodies' region modalities read are run (:338-339).
+ *   - every RegionModality of a listed body does RegionModality::StartModality(iteration, 0)
+ *     (region_modality.cpp:375-388): first_iteration = iteration, the histograms initialised from the current frame at
+ *     the new pose with handle_occlusions = (n_unoccluded_iterations == 0).  DepthModalities: what start_modalities
+ *     does for them (nothing to restart).
+ * Everything else stays as it was, bit for bit: the other bodies' poses, histograms, first_iteration, line and point
+ * state and the g/H of the last step.  The compact kernel's table-overflow latch (the step kernel with the LDS pair
+ * table steps aside once histograms outgrow the table; start_modalities re-arms it) is left alone: it selects a
+ * kernel, the poses do not depend on it.  State that follows a body's pose is left as body_set_body2world_pose +
+ * start_modalities leave it: the next step's ROI rectangles start from a fresh snapshot of the poses, and a step
+ * that reads rectangles cut around the old pose repeats the reset bodies on whole frames, as after a pose set by the
+ * host.  The view-search hint of the modality is only a starting point (the search falls back to the full scan when
+ * the direction left the hinted view's neighbourhood) and is not touched by either.
+ * The call is enqueued on the context's stream: with device-authoritative poses it reads no pose back, does not wait
+ * for the stream and uploads no table again; the few words it changes are written by a kernel and the host mirrors
+ * follow.  (Tables and host-set poses that were already waiting for their upload are uploaded as by any other call.)
+ * Arguments are checked before anything changes; a failed call leaves the context as it was:
+ *   M3T_ERR_INVALID_ARGUMENT  n < 0, an id out of range, an id listed twice;  n == 0: M3T_OK, nothing happens
+ *   M3T_ERR_UNSUPPORTED       a listed body in a structure of more than one link; a RegionModality of a listed body
+ *                             that uses shared ColorHistograms (the reference's ResetBody leaves the shared object
+ *                             half-updated there); ROI ingest: a camera read by a LISTED body's modality whose current
+ *                             slot holds a rectangle only -- upload whole frames for those cameras alone.
+ * A body without modalities only gets its pose. */
+int m3t_hip_reset_bodies(m3t_hip_context*, const int* body_ids, const float* body2world_poses /* n x 16, or NULL */,
+                         int n, int iteration);
 int m3t_hip_calculate_correspondences(m3t_hip_context*, int iteration, int corr_iteration); /* :447 */
 int m3t_hip_calculate_gradient_and_hessian(m3t_hip_context*, int iteration, int corr_iteration,
                                            int opt_iteration);                    /* :471 */

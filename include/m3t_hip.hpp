@@ -449,6 +449,15 @@ class Tracker {
     return c_->Step(m3t_hip_refine_poses(c_->get(), n_corr_iterations, n_update_iterations));
   }
   bool Sync() { return c_->Step(m3t_hip_sync(c_->get())); }
+  // RBOTEvaluator::ResetBody (rbot_evaluator.cpp:334-352) for the listed bodies alone (m3t_hip_reset_bodies): their poses
+  // (empty: the poses stay), their start-modality renderers, StartModality(iteration) of their region modalities
+  bool ResetBodies(const std::vector<const Body*>& bodies, const std::vector<Pose>& poses = {}, int iteration = 0) {
+    if (!poses.empty() && poses.size() != bodies.size()) return false;
+    std::vector<int> body_ids;
+    for (const Body* body : bodies) body_ids.push_back(body->id());
+    return c_->Step(m3t_hip_reset_bodies(c_->get(), body_ids.data(), poses.empty() ? nullptr : poses[0].data(),
+                                         int(body_ids.size()), iteration));
+  }
 
   // ---- the batch at once, and what has no counterpart in the reference (m3t_hip.h) ----
   // poses of the first n bodies in creation order, one copy each way

@@ -1,8 +1,10 @@
 """examples/evaluate_rbot_dataset.cpp over the device context (region modality, sequences without modelled
 occlusions):
 
-    python tools/evaluate_rbot_dataset.py RBOT_DATASET_DIR EXTERNAL_DIR [body ...]
+    python tools/evaluate_rbot_dataset.py [--batch N] RBOT_DATASET_DIR EXTERNAL_DIR [body ...]
 
+--batch N: up to N runs share one device context (each with its own body, model, camera and optimizer); a lost body is
+reset alone (m3t_hip_reset_bodies), so the results are those of one context per run.
 Prints the success rate and the mean step time per (sequence, body) and overall, like
 RBOTEvaluator::VisualizeFinalResult."""
 import importlib
@@ -24,9 +26,18 @@ rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE",
 local_rank = int(os.environ.get("LOCAL_RANK", "0"))
 
 if __name__ == "__main__":
-    if len(sys.argv) < 3:
-        sys.exit("usage: evaluate_rbot_dataset.py RBOT_DATASET_DIR EXTERNAL_DIR [body ...]")
+    argv = sys.argv[1:]
+    batch = 1
+    if "--batch" in argv:
+        at = argv.index("--batch")
+        if at + 1 >= len(argv) or not argv[at + 1].isdigit() or int(argv[at + 1]) < 1:
+            sys.exit("--batch takes a positive number of runs per context")
+        batch = int(argv[at + 1])
+        del argv[at:at + 2]
+    if len(argv) < 2:
+        sys.exit("usage: evaluate_rbot_dataset.py [--batch N] RBOT_DATASET_DIR EXTERNAL_DIR [body ...]")
     ev = pkg.evaluation
-    bodies = sys.argv[3:] or ev.RBOT_BODY_NAMES
-    _, overall = ev.evaluate_rbot_dataset(lambda: pkg.open_context(local_rank), sys.argv[1], sys.argv[2], bodies, report=report, shard=(rank, world))
+    bodies = argv[2:] or ev.RBOT_BODY_NAMES
+    _, overall = ev.evaluate_rbot_dataset(lambda: pkg.open_context(local_rank), argv[0], argv[1], bodies, report=report,
+                                          shard=(rank, world), batch=batch)
     report("all_sequences_all_bodies", overall)
