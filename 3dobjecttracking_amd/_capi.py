@@ -321,6 +321,7 @@ _HIP_ONLY = {
     "get_kernel_timing": [c_float_p, c_int_p],
     "get_step_shape": [c_int_p],
     "get_step_kernel": [C.c_char_p, C.c_size_t],
+    "get_step_variant": [C.c_char_p, C.c_size_t],
     "debug_log_checksum": [C.c_uint, C.c_uint, C.POINTER(C.c_ulonglong)],
     "set_object_split": [C.c_int],
     "reset_bodies": [c_int_p, c_float_p, C.c_int, C.c_int],
@@ -349,7 +350,7 @@ def pose_ret(buf):
     return np.array(buf, dtype=np.float32).reshape(4, 4).T.copy()
 
 
-_NEWER_ENTRY_POINTS = ("comm_set_reduce_callback", "get_step_kernel", "comm_get_allreduce_count", "comm_get_rank_count", "debug_log_checksum", "set_roi_ingest",
+_NEWER_ENTRY_POINTS = ("comm_set_reduce_callback", "get_step_kernel", "get_step_variant", "comm_get_allreduce_count", "comm_get_rank_count", "debug_log_checksum", "set_roi_ingest",
                        "cameras_upload_batch_roi_async", "roi_get_status", "roi_get_unrecovered", "reserve_ingest_cus", "camera_slot_sync")
 
 

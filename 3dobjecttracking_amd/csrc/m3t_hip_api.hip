@@ -268,6 +268,7 @@ struct m3t_hip_context {
   bool compact_possible = false;       // every modality fits the kernel's assumptions (UploadTables)
   bool compact_fuses_histogram = false;  // ... and the count table fits next to the scratch block (<= 16 bins)
   const char* last_step_kernel = "";   // m3t_hip_get_step_kernel
+  bool last_step_moments_first = false;  // m3t_hip_get_step_variant: the split kernel's moments-first instantiation
   // ROI ingest (m3t_ingest.hip): rectangles instead of whole frames
   bool roi_enabled = false;        // m3t_hip_set_roi_ingest
   bool roi_adaptive = false;       // ... with enable = 2: per-body margins from the motion over the last step
@@ -1527,6 +1528,8 @@ int UploadTables(Ctx* ctx) {
     for (auto& m : ctx->region_mods)
       if (m->shared_histograms >= 0 || m->p.n_histogram_bins < 4) ctx->split_possible = false;
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(tracking_step_split_kernel),
+                               hipFuncAttributeMaxDynamicSharedMemorySize, int(std::max(ctx->lds_track, ctx->lds_hist))));
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(tracking_step_split_moments_kernel),
                                hipFuncAttributeMaxDynamicSharedMemorySize, int(std::max(ctx->lds_track, ctx->lds_hist))));
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(tracking_step_split_render_kernel),
                                hipFuncAttributeMaxDynamicSharedMemorySize, int(std::max(ctx->lds_track, ctx->lds_hist))));
@@ -4037,6 +4040,7 @@ int m3t_hip_execute_tracking_step(m3t_hip_context* ctx, int iteration) {
   ctx->untracked_launches = untracked_before;  // a whole step is tracked by its step_done event below
   if ((r = CheckSplitExchange(ctx))) return r;  // an earlier step that was abandoned on the device
   bool histogram_fused = false;
+  ctx->last_step_moments_first = false;
   const bool rigid_fused = ctx->fused_mode >= 1 && ctx->fused_possible && !ctx->Distributed();
   bool roi_frames = false;  // does this step read a slot that holds a rectangle only
   for (auto& cam : ctx->cameras) roi_frames = roi_frames || cam->slot_is_roi[cam->current];
@@ -4092,7 +4096,17 @@ int m3t_hip_execute_tracking_step(m3t_hip_context* ctx, int iteration) {
     // Batches with region AND depth modalities: the _pair_ kernels (m3t_kernels.hip, PAIR: the two modalities' products
     // side by side, their sums on two waves).  M3T_HIP_NO_PAIR: developer override.
     const bool pair = !roi_frames && !ctx->region_mods.empty() && !ctx->depth_mods.empty() && !std::getenv("M3T_HIP_NO_PAIR");
-    auto split_kernel = pair ? tracking_step_split_pair_kernel : tracking_step_split_kernel;
+    // Region-only batches whose first Newton step after a search reads no distribution row (n_global_iterations >= 1)
+    // and whose searches have no occlusion vote to defer: the split kernel with the moments-first exchange
+    // (m3t_kernels.hip, split_exchange_publish_moments).  Every object of the launch must qualify; all others keep
+    // tracking_step_split_kernel.  M3T_HIP_NO_MOMENTS_FIRST: developer override.
+    bool moments_first = !roi_frames && !pair && ctx->depth_mods.empty() && !ctx->region_mods.empty() &&
+                         ctx->n_update_iterations >= 1 && !std::getenv("M3T_HIP_NO_MOMENTS_FIRST");
+    for (auto& m : ctx->region_mods)
+      if (m->dev.measure_occlusions || m->dev.model_occlusions || m->dev.use_region_checking || m->dev.n_global_iterations < 1)
+        moments_first = false;
+    auto split_kernel = pair ? tracking_step_split_pair_kernel
+                             : (moments_first ? tracking_step_split_moments_kernel : tracking_step_split_kernel);
     auto kernel = pair ? (ctx->layout.off_hist >= 0 ? tracking_step_lds_pair_kernel : tracking_step_pair_kernel)
                        : (ctx->layout.off_hist >= 0 ? tracking_step_lds_kernel : tracking_step_kernel);
     // One workgroup per CU: the histogram update (CalculateResults) runs at the end of the same launch, its
@@ -4112,6 +4126,7 @@ int m3t_hip_execute_tracking_step(m3t_hip_context* ctx, int iteration) {
                          : ChooseSplitParts(ctx, split_kernel, n, threads,
                                             want_fused_histogram, &lds_split);
     const bool split = parts >= 2;
+    ctx->last_step_moments_first = split && moments_first;
     // More objects than CUs: the compact kernel (<= 47 KB of LDS, <= 128 VGPRs per object: 3-4 workgroups per CU;
     // measured crossover on 256 CUs: 256 objects 0.249 vs 0.225 ms with one 512-thread workgroup per CU, 384 objects
     // 0.309 vs 0.426 ms).  M3T_HIP_COMPACT=0 / 1: developer override (never / whenever possible).
@@ -4558,6 +4573,12 @@ int m3t_hip_get_step_kernel(m3t_hip_context* ctx, char* name, size_t capacity) {
   std::snprintf(name, capacity, "%s", ctx->last_step_kernel);
   return M3T_OK;
 }
+int m3t_hip_get_step_variant(m3t_hip_context* ctx, char* name, size_t capacity) {
+  CHECK_CTX();
+  REQUIRE(name && capacity > 0, M3T_ERR_INVALID_ARGUMENT, "null output");
+  std::snprintf(name, capacity, "%s", ctx->last_step_moments_first ? "tracking_step_split_moments_kernel" : ctx->last_step_kernel);
+  return M3T_OK;
+}
 int m3t_hip_get_kernel_timing(m3t_hip_context* ctx, float total_ms[2], int launches[2]) {
   CHECK_CTX();
   HIPCHK(hipSetDevice(ctx->device));
@@ -4586,12 +4607,13 @@ int m3t_hip_get_kernel_timing(m3t_hip_context* ctx, float total_ms[2], int launc
   return M3T_OK;
 }
 #ifdef M3T_PHASE_TIMING
-int m3t_hip_debug_phase_cycles(m3t_hip_context* ctx, unsigned long long* out24, int reset) {
+int m3t_hip_debug_phase_rows(void) { return M3T_PHASE_ROWS; }  // how many values m3t_hip_debug_phase_cycles writes
+int m3t_hip_debug_phase_cycles(m3t_hip_context* ctx, unsigned long long* out, int reset) {
   CHECK_CTX();
   HIPCHK(hipStreamSynchronize(ctx->stream));
-  HIPCHK(hipMemcpyFromSymbol(out24, HIP_SYMBOL(g_phase_cycles), 32 * sizeof(unsigned long long)));
+  HIPCHK(hipMemcpyFromSymbol(out, HIP_SYMBOL(g_phase_cycles), M3T_PHASE_ROWS * sizeof(unsigned long long)));
   if (reset) {
-    unsigned long long z[32] = {0};
+    unsigned long long z[M3T_PHASE_ROWS] = {0};
     HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(g_phase_cycles), z, sizeof(z)));
   }
   return M3T_OK;

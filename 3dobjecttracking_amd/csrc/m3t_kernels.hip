@@ -13,6 +13,8 @@
 //   tracking_step_kernel (+ _lds_); launched with 256-thread workgroups, two per CU, from two objects per CU on
 //                             the whole ExecuteTrackingStep loop nest fused on device
 //   tracking_step_split_kernel the same with 4 / 8 / 16 workgroups per object (batches that leave CUs idle)
+//   tracking_step_split_moments_kernel the split kernel for Region-only objects whose first Newton step behind a search
+//                             is a global one: the lines' means and variances cross first, the distributions beside the solve
 //   (kinematic structures: m3t_links.hip)
 //
 // Arithmetic follows the reference expression by expression in IEEE f32
@@ -31,15 +33,21 @@
 #include "m3t_renderer_read.h"
 #include "m3t_roi.h"
 
+#define M3T_PHASE_ROWS 40  // rows of the phase table (m3t_hip_debug_phase_cycles copies as many)
 #ifdef M3T_PHASE_TIMING
 // developer instrumentation: accumulated s_memtime cycles per phase, block 0 thread 0
-__device__ unsigned long long g_phase_cycles[32];
+__device__ unsigned long long g_phase_cycles[M3T_PHASE_ROWS];
 __device__ unsigned long long g_exchange_times[3 * 16 * 16];  // [kind][round][part] of object 0, last frame
 #define EXCHANGE_STAMP(kind, round, part, object)                                                      \
   do {                                                                                                 \
     if ((object) == 0 && threadIdx.x == 0 && (round) < 16 && (part) < 16)                              \
       g_exchange_times[((kind) * 16 + (round)) * 16 + (part)] = clock64();                             \
   } while (0)
+#ifdef M3T_EXCHANGE_STAMPS_ONLY  // (tools/exchange_waits.py: the stamps without the phase marks' clock reads)
+#define PHASE_T0() do {} while (0)
+#define PHASE_MARK(i) do {} while (0)
+#define PHASE_MARK_BY(i, thread) do {} while (0)
+#else
 #define PHASE_T0() unsigned long long _pt = clock64()
 #define PHASE_MARK(i)                                                         \
   do {                                                                        \
@@ -54,6 +62,7 @@ __device__ unsigned long long g_exchange_times[3 * 16 * 16];  // [kind][round][p
     if (blockIdx.x == 0 && (int)threadIdx.x == (thread)) g_phase_cycles[i] += _n - _pt; \
     _pt = _n;                                                                           \
   } while (0)
+#endif
 #else
 #define EXCHANGE_STAMP(kind, round, part, object) do {} while (0)
 #define PHASE_T0() do {} while (0)
@@ -700,7 +709,7 @@ __device__ __forceinline__ void region_segments(CRegion& m, G<uint8_t> image, ui
     }
     PHASE_MARK(7);  // LDS reads + address arithmetic + pixel load issue
     v2f h[B][SCALE];
-#ifdef M3T_PHASE_TIMING
+#if defined(M3T_PHASE_TIMING) && !defined(M3T_EXCHANGE_STAMPS_ONLY)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     PHASE_MARK(8);  // pixel load latency
 #endif
@@ -714,7 +723,7 @@ __device__ __forceinline__ void region_segments(CRegion& m, G<uint8_t> image, ui
                        (((v >> 16) & 0xffu) >> bitshift);
         h[b][j] = load_pair(hist, idx);
       }
-#ifdef M3T_PHASE_TIMING
+#if defined(M3T_PHASE_TIMING) && !defined(M3T_EXCHANGE_STAMPS_ONLY)
     PHASE_MARK(9);  // histogram gather issue
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     PHASE_MARK(10);  // histogram gather latency
@@ -1451,6 +1460,10 @@ __device__ __forceinline__ void region_products(CRegion& m, CCam& cam, const Aff
 // granules: one write-through store each, re-read by the others until the tag matches.  The data is the flag, no
 // fence (cdna_hip_programming.md guideline 16, form R2).  Slots alternate with the round: a workgroup can only be
 // one round ahead of another, because it cannot leave a round before it has read everybody's granules of it.
+// (The moments-first exchange further down collects a round's distribution rows late, beside the first Newton step
+// behind the search -- but joins that collect at the barrier behind that step's solve, before the next search: a part
+// still holds every granule of round c before it publishes anything of round c + 1, and whoever published in round c
+// had collected all of round c - 1, whose slot round c + 1 overwrites.)
 // From there on every workgroup holds the same line / point state, forms the same sums in the reference's order
 // and solves the same system: no exchange inside the Newton steps, bit-identical poses in every workgroup.
 // A wait that runs out (a partner that is not resident: another process on the GPU) ends the whole object's step
@@ -1570,6 +1583,139 @@ __device__ __forceinline__ bool split_exchange_collect(const SplitExchange& x, i
     return false;
   }
   return true;
+}
+
+// ---------------------------------------------------------------------------
+// Moments-first exchange (tracking_step_split_moments_kernel: Region-only objects, no deferred occlusion vote,
+// n_global_iterations >= 1).  The first Newton step after a search takes the global branch of region_products, which
+// reads a line's mean and variance but not its distribution; so only those two values per line sit on the critical
+// path: the part that owns a line takes its moments (the same code on the same bits a receiver would run) and sends
+// them as the fields distribution_length and distribution_length + 1 of its slot, and the distribution rows
+// -- sent by phase C2 as before -- are collected by the waves that would otherwise wait at the barrier behind the first
+// Newton step's chain and solve (wave 0).  That barrier is the join: no part publishes anything of round c + 1 before
+// it holds every granule of round c, which is what the alternating slots need (see above).
+// ---------------------------------------------------------------------------
+// the moments of the own lines [lo, hi), and their granules; no barrier (every thread sends what it wrote itself).
+// Lines beyond the view's lines and invalid lines send what their row holds: the receivers wait for every granule.
+__device__ __forceinline__ void split_exchange_publish_moments(const SplitExchange& x, int round, CRegion& m, const Lds& s,
+                                                               int lo, int hi) {
+  region_moments(m, s, lo, hi, true);
+  const int nl = s.nl, f_mean = m.distribution_length;
+  auto* mine = x.granules + (((size_t)(round & 1) * x.n_parts + x.part) << (kExchangeFieldBits + x.lshift));
+  const unsigned long long tag_bits = static_cast<unsigned long long>(x.seq * 64u + (uint32_t)round + 1u) << 32;
+  for (int line = threadIdx.x; line < nl; line += blockDim.x) {  // (the thread -> line map of region_moments_lines)
+    if (line < lo || line >= hi) continue;
+    const float mean = s.state[LS_MEAN * nl + line], var = s.state[LS_VAR * nl + line];
+    __hip_atomic_store(mine + ((f_mean << x.lshift) | (line - lo)), tag_bits | (unsigned)__float_as_int(mean),
+                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(mine + (((f_mean + 1) << x.lshift) | (line - lo)), tag_bits | (unsigned)__float_as_int(var),
+                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+// what a waiting thread does with a granule that has not arrived: poll it again, give up after ~5 ms or when another
+// workgroup of the object has (split_exchange_collect's wait, as a function for the two collects below; they read
+// every field of the descriptor ONCE, into locals: with a read per use the compiler kept part of it in scratch memory)
+__device__ __forceinline__ unsigned long long split_exchange_wait(__attribute__((address_space(1))) unsigned* object_abort,
+                                                                  uint32_t seq, uint32_t tag,
+                                                                  __attribute__((address_space(1))) unsigned long long* p,
+                                                                  unsigned long long g, bool& timed_out) {
+  unsigned spins = 0;
+  while (static_cast<uint32_t>(g >> 32) != tag) {
+    if (++spins > (1u << 12) ||
+        ((spins & 255u) == 0 && __hip_atomic_load(object_abort, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == seq)) {
+      timed_out = true;
+      break;
+    }
+    __builtin_amdgcn_s_sleep(1);
+    g = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  return g;
+}
+__device__ __forceinline__ bool split_exchange_abort_check(const SplitExchange& x, bool timed_out) {  // a barrier
+  if (__syncthreads_or(timed_out ? 1 : 0)) {
+    if (threadIdx.x == 0) {
+      __hip_atomic_store(x.object_abort, x.seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_store(x.host_abort, x.abort_id, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+    return false;
+  }
+  return true;
+}
+// the other parts' means and variances: thread -> (part q, element l) as in split_exchange_collect, one granule per
+// thread at 512 threads (two at 256).  A received value is stored where region_moments would have stored one: for
+// valid lines.  Returns false when the exchange timed out (block-uniform); ends with a barrier.
+__device__ __forceinline__ bool split_exchange_collect_moments(const SplitExchange& x, int round, CRegion& m, const Lds& s) {
+  const int tid = threadIdx.x, nt = blockDim.x, nl = s.nl;
+  const int lshift = x.lshift, n_parts = x.n_parts, per_part = x.per_part_lines, part = x.part;
+  const uint32_t seq = x.seq, tag = seq * 64u + (uint32_t)round + 1u;
+  auto* const object_abort = x.object_abort;
+  const int lanes = n_parts << lshift;
+  const int ql = tid & (lanes - 1);
+  const int q = ql >> lshift, l = ql & ((1 << lshift) - 1);
+  const int n_groups = nt / lanes, group = __builtin_amdgcn_readfirstlane(tid / lanes);
+  const int e = q * per_part + l;
+  const bool ok = q != part && l < per_part && e < nl;
+  auto* theirs = x.granules +
+                 (((((size_t)(round & 1) * n_parts + q) << kExchangeFieldBits) + m.distribution_length) << lshift) + l;
+  const int j0 = group, j1 = group + n_groups;  // 0: mean, 1: variance
+  bool timed_out = false;
+  unsigned long long g0 = 0, g1 = 0;
+  if (ok && j0 < 2) g0 = __hip_atomic_load(theirs + ((size_t)j0 << lshift), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (ok && j1 < 2) g1 = __hip_atomic_load(theirs + ((size_t)j1 << lshift), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  const bool valid = ok && (f2i_bits(s.state[LS_VALID * nl + e]) & 1);
+  if (ok && j0 < 2) {
+    g0 = split_exchange_wait(object_abort, seq, tag, theirs + ((size_t)j0 << lshift), g0, timed_out);
+    if (valid) s.state[(j0 == 0 ? LS_MEAN : LS_VAR) * nl + e] = __int_as_float(static_cast<int>(static_cast<uint32_t>(g0)));
+  }
+  if (ok && j1 < 2) {
+    g1 = split_exchange_wait(object_abort, seq, tag, theirs + ((size_t)j1 << lshift), g1, timed_out);
+    if (valid) s.state[(j1 == 0 ? LS_MEAN : LS_VAR) * nl + e] = __int_as_float(static_cast<int>(static_cast<uint32_t>(g1)));
+  }
+  return split_exchange_abort_check(x, timed_out);
+}
+// the other parts' distribution rows, by the threads from first_thread on (whole waves) while the first wave runs the
+// chain and the solve: item i = field (i / 256) of lane (i % 256), the field index wave-uniform; batches of eight
+// granules per thread, all loads of a batch issued before the first tag is looked at.  No barrier; returns whether a
+// wait ran out (the caller joins: split_exchange_abort_check).  Writes the rows LS_DIST0.. of s.state only.
+__device__ __forceinline__ bool split_exchange_collect_rows(const SplitExchange& x, int round, const Lds& s, int first_thread) {
+  static_assert(M3T_SPLIT_LANES == 256, "item -> (field, lane) below");
+  const int t = (int)threadIdx.x - first_thread, nc = (int)blockDim.x - first_thread, nl = s.nl;
+  const int lshift = x.lshift, per_part = x.per_part_lines, part = x.part;
+  const uint32_t seq = x.seq, tag = seq * 64u + (uint32_t)round + 1u;
+  auto* const object_abort = x.object_abort;
+  const int lmask = (1 << lshift) - 1;
+  const int n_items = x.n_region_fields << 8;
+  auto* slot = x.granules + ((size_t)(round & 1) * x.n_parts << (kExchangeFieldBits + lshift));
+  float* rows = s.state + x.first_region_row * nl;
+  bool timed_out = false;
+  for (int i0 = t; i0 < n_items; i0 += 8 * nc) {
+    unsigned long long g0 = 0, g1 = 0, g2 = 0, g3 = 0, g4 = 0, g5 = 0, g6 = 0, g7 = 0;
+#define M3T_ROWS_ITEM(J)                                                                                             \
+      const int i = i0 + J * nc, f = i >> 8, q = (i & 255) >> lshift, l = i & lmask, e = q * per_part + l;            \
+      const bool ok = i < n_items && q != part && l < per_part && e < nl;                                             \
+      auto* p = slot + ((size_t)((q << kExchangeFieldBits) + f) << lshift) + l;
+#define M3T_ROWS_LOAD(J, G)                                                                                          \
+      {                                                                                                              \
+        M3T_ROWS_ITEM(J)                                                                                             \
+        if (ok) G = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);                                \
+      }
+#define M3T_ROWS_WAIT(J, G)                                                                                          \
+      {                                                                                                              \
+        M3T_ROWS_ITEM(J)                                                                                             \
+        if (ok) {                                                                                                    \
+          G = split_exchange_wait(object_abort, seq, tag, p, G, timed_out);                                          \
+          rows[f * nl + e] = __int_as_float(static_cast<int>(static_cast<uint32_t>(G)));                             \
+        }                                                                                                            \
+      }
+    M3T_ROWS_LOAD(0, g0) M3T_ROWS_LOAD(1, g1) M3T_ROWS_LOAD(2, g2) M3T_ROWS_LOAD(3, g3)
+    M3T_ROWS_LOAD(4, g4) M3T_ROWS_LOAD(5, g5) M3T_ROWS_LOAD(6, g6) M3T_ROWS_LOAD(7, g7)
+    M3T_ROWS_WAIT(0, g0) M3T_ROWS_WAIT(1, g1) M3T_ROWS_WAIT(2, g2) M3T_ROWS_WAIT(3, g3)
+    M3T_ROWS_WAIT(4, g4) M3T_ROWS_WAIT(5, g5) M3T_ROWS_WAIT(6, g6) M3T_ROWS_WAIT(7, g7)
+#undef M3T_ROWS_ITEM
+#undef M3T_ROWS_LOAD
+#undef M3T_ROWS_WAIT
+  }
+  return timed_out;
 }
 
 // ---------------------------------------------------------------------------
@@ -3056,7 +3202,10 @@ extern "C++" {
 // each in the reference's order, added like Link::CalculateGradientAndHessian adds them.  A template parameter, not a
 // run-time choice: the Region-only step keeps its machine code (with the choice inside, tracking_step_split_kernel went
 // from 234 to 241 VGPRs and the 64-object headline from 0.149 to 0.151 ms).
-template <bool HIST_LDS, bool SPLIT = false, bool RENDER = !SPLIT, bool GUARD = false, bool PAIR = false>
+// MOMENTS_FIRST (tracking_step_split_moments_kernel): the moments-first exchange (split_exchange_publish_moments and what
+// follows it) -- a template parameter for the same reason.
+template <bool HIST_LDS, bool SPLIT = false, bool RENDER = !SPLIT, bool GUARD = false, bool PAIR = false,
+          bool MOMENTS_FIRST = false>
 __device__ __forceinline__ void tracking_step_body(const RigidOptDev* opts, const RegionModDev* rmods, const DepthModDev* dmods,
                      const CameraDev* cams, float* body_poses, TrackLdsLayout layout, int off_points, int np,
                      int iteration, int n_corr_iterations, int n_update_iterations, int write_state,
@@ -3163,7 +3312,17 @@ __device__ __forceinline__ void tracking_step_body(const RigidOptDev* opts, cons
                                            (rm && dm->view_search_shared) ? region_view : -1);
         PHASE_MARK(16);
       }
-      if constexpr (SPLIT) {
+      if constexpr (MOMENTS_FIRST) {
+        // (the host vouches: Region-only, no occlusion pass, n_global_iterations >= 1)
+        PHASE_T0();
+        EXCHANGE_STAMP(0, c, part, object);
+        split_exchange_publish_moments(exchange, c, *rm, s, line_lo, line_hi);
+        EXCHANGE_STAMP(1, c, part, object);
+        PHASE_MARK(30);  // owner moments
+        if (!split_exchange_collect_moments(exchange, c, *rm, s)) return;
+        EXCHANGE_STAMP(2, c, part, object);
+        PHASE_MARK(31);  // moments wait
+      } else if constexpr (SPLIT) {
         PHASE_T0();
         // with occlusion handling on, the flags of the own lines (their occlusion results) travel too and the vote
         // over all lines follows the exchange (region_correspondences, defer_vote)
@@ -3188,10 +3347,11 @@ __device__ __forceinline__ void tracking_step_body(const RigidOptDev* opts, cons
         } else if (rm) {
           region_moments(*rm, s, line_lo, line_hi, false);
         }
+        PHASE_MARK(25);  // (the moments of the received lines)
       } else {
         if (rm) region_moments(*rm, s);
       }
-      {
+      if constexpr (!MOMENTS_FIRST) {  // (moments-first: the collect's barrier is the one in front of the products)
         PHASE_T0();
         if (dm) depth_correspondences_vote<RENDER>(*dm, iteration, ps, np, s.misc);
         else __syncthreads();
@@ -3290,7 +3450,25 @@ __device__ __forceinline__ void tracking_step_body(const RigidOptDev* opts, cons
         PHASE_MARK(23);
         rigid_solve_wave(gh, o.tikhonov_rotation, o.tikhonov_translation, (LdsW)pose, (LdsW)(s.misc + kMiscSolve));
       }
-      __syncthreads();
+      if constexpr (MOMENTS_FIRST) {
+        // the search's distribution rows, needed from the next Newton step on (local branch of region_products, state
+        // write-back): collected beside the first step's chain and solve, joined by the barrier behind them
+        if (u == 0) {
+          // (every wave but the first collects: waves 2-7 or 4-7 alone measured the same, 6-7 alone are late at the join;
+          // profiles/r07_split_moments_first.txt.  A split launch has a multiple of 256 threads: collectors exist.)
+          const int first = kWave;
+          bool timed_out = false;
+          if ((int)threadIdx.x >= first) {
+            timed_out = split_exchange_collect_rows(exchange, c, s, first);
+            PHASE_MARK_BY(32, first);  // deferred collect (its first wave; from the barrier behind the products)
+          }
+          if (!split_exchange_abort_check(exchange, timed_out)) return;
+        } else {
+          __syncthreads();
+        }
+      } else {
+        __syncthreads();
+      }
       PHASE_MARK(6);
     }
   }
@@ -3376,6 +3554,17 @@ tracking_step_split_kernel(const RigidOptDev* opts, const RegionModDev* rmods, c
                      int fuse_histogram, SplitParams split) {
   tracking_step_body<false, true>(opts, rmods, dmods, cams, body_poses, layout, off_points, np, iteration,
                                   n_corr_iterations, n_update_iterations, write_state, fuse_histogram, &split);
+}
+
+// Region-only objects without an occlusion pass and with n_global_iterations >= 1: the moments-first exchange
+__global__ void __launch_bounds__(M3T_BLOCK_THREADS)
+tracking_step_split_moments_kernel(const RigidOptDev* opts, const RegionModDev* rmods, const DepthModDev* dmods,
+                     const CameraDev* cams, float* body_poses, TrackLdsLayout layout, int off_points, int np,
+                     int iteration, int n_corr_iterations, int n_update_iterations, int write_state,
+                     int fuse_histogram, SplitParams split) {
+  tracking_step_body<false, true, false, false, false, true>(opts, rmods, dmods, cams, body_poses, layout, off_points, np,
+                                                             iteration, n_corr_iterations, n_update_iterations, write_state,
+                                                             fuse_histogram, &split);
 }
 
 // Bodies with a RegionModality and a DepthModality: the same three kernels with PAIR (tracking_step_body): ycb21 0.157 ->

@@ -402,6 +402,10 @@ int m3t_hip_debug_log_checksum(m3t_hip_context*, unsigned first_bits, unsigned l
 int m3t_hip_set_kernel_timing(m3t_hip_context*, int enable);
 /* name of the kernel the last execute_tracking_step launched for the tracking loop ("" = one launch per sub-step) */
 int m3t_hip_get_step_kernel(m3t_hip_context*, char* name, size_t capacity);
+/* the same, down to the instantiation: "tracking_step_split_moments_kernel" where get_step_kernel says
+ * "tracking_step_split_kernel" and the launch was the one with the moments-first exchange (Region-only objects without
+ * an occlusion pass, n_global_iterations >= 1); everywhere else what get_step_kernel says */
+int m3t_hip_get_step_variant(m3t_hip_context*, char* name, size_t capacity);
 int m3t_hip_get_kernel_timing(m3t_hip_context*, float total_ms[2], int launches[2]);
 /* launch shape of the last fused tracking step: [0] objects, [1] workgroups per object (1, or 4 / 8 / 16 =
  * tracking_step_split_kernel when the batch leaves CUs idle), [2] threads per workgroup,

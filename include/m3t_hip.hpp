@@ -568,6 +568,11 @@ class Tracker {
     c_->Check(m3t_hip_get_step_kernel(c_->get(), name, sizeof(name)), "Tracker");
     return name;
   }
+  std::string StepVariant() const {  // the same down to the instantiation (m3t_hip_get_step_variant)
+    char name[64] = {0};
+    c_->Check(m3t_hip_get_step_variant(c_->get(), name, sizeof(name)), "Tracker");
+    return name;
+  }
   std::array<int, 4> StepShape() const {
     std::array<int, 4> shape{};
     c_->Check(m3t_hip_get_step_shape(c_->get(), shape.data()), "Tracker");

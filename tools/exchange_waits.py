@@ -2,6 +2,11 @@
 build: the exchange stamps without the phase marks).  Per correspondence iteration and part of object 0, last frame:
 publish = stamp(published) - stamp(publish start), wait = stamp(collected) - stamp(published).  (s_memtime bases
 differ between CUs: only differences of one part's own stamps mean anything.)
+tracking_step_split_kernel: publish = what phase C2 has not sent yet, wait = the own lines' moments + the round trip of the
+distribution rows + the barrier.  tracking_step_split_moments_kernel (the line below names the launch): publish = the
+own lines' moments and their two granules per line, wait = the round trip of the means and variances + the barrier; the
+distribution rows are collected beside the first Newton step and show up in "collected -> next publish start" only if
+they are late.
   python tools/exchange_waits.py <lib> [objects]"""
 import ctypes as C, importlib, os, sys
 os.environ.setdefault("M3T_INPUT_WORKERS", "auto")
@@ -26,7 +31,9 @@ for k in range(1, 8):
     parts = shape[1]
     if k < 5:
         continue
-    print("frame %d, %d parts" % (k, parts))
+    name = C.create_string_buffer(64)
+    hip.call("get_step_variant" if "get_step_variant" in hip._fn else "get_step_kernel", name, 64)
+    print("frame %d, %d parts, %s" % (k, parts, name.value.decode()))
     for rnd in range(7):
         start = [xt[(0 * 16 + rnd) * 16 + p] for p in range(parts)]
         pub = [xt[(1 * 16 + rnd) * 16 + p] for p in range(parts)]

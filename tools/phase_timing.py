@@ -19,7 +19,8 @@ inputs = scenes.Inputs(n_obj, 8, n_divides=4, n_models=min(8, n_obj), with_depth
 inst = scenes.Instance(hip, inputs, use_depth=ycb)
 inst.upload_frame(0)
 inst.tracker.StartModalities(0)
-buf = (C.c_ulonglong * 32)()
+hip.lib.m3t_hip_debug_phase_rows.restype = C.c_int
+buf = (C.c_ulonglong * hip.lib.m3t_hip_debug_phase_rows())()  # M3T_PHASE_ROWS of the library
 for k in range(1, 4):
     inst.upload_frame(k); inst.tracker.ExecuteTrackingStep(k)
 f(hip.ctx, buf, 1)
@@ -34,8 +35,15 @@ names = ["view search", "phase A (lines)", "phase B (pixels)", "phase C1 (dist)"
          "  d: view search", "  d: point setup", "  d: window scan", "  d: reduce+occlusion", "  d: write",
          "split exchange", "g/H chain (42 lanes)", "g/H products + barrier (u>=1, local)", "moments / depth vote",
          "histogram update (tail)"]
-tot = sum(buf[i] for i in range(7)) + buf[16] + sum(buf[22:27])
+# rows 27-29: the tail's parts (printed below).  Moments-first exchange (tracking_step_split_moments_kernel), in place of
+# "split exchange" and "moments / depth vote"; the deferred collect runs on another wave BESIDE the chain and the solve
+# (from the barrier behind the products of u = 0 to its last granule) and is not part of the total
+extra = {30: "owner moments + their granules", 31: "moments wait (round trip + barrier)",
+         32: "  deferred collect (collecting wave)"}
+tot = sum(buf[i] for i in range(7)) + buf[16] + sum(buf[22:27]) + buf[30] + buf[31]
 for i, nme in enumerate(names):
+    print("%-38s %10.0f cycles/frame  %5.1f%%" % (nme, buf[i] / n, 100.0 * buf[i] / tot))
+for i, nme in sorted(extra.items()):
     print("%-38s %10.0f cycles/frame  %5.1f%%" % (nme, buf[i] / n, 100.0 * buf[i] / tot))
 print("total %.0f cycles/frame" % (tot / n))
 print("tail: view search %.0f, occlusion windows %.0f, pixel walk %.0f cycles/frame (blend = the rest)" %
@@ -51,6 +59,8 @@ try:
     hip.call("get_step_shape", shape)
     parts = shape[1]
     if parts > 1:
+        # (moments-first exchange: publish start = the own lines' moments begin, published = their granules are out,
+        # collected = the other parts' means and variances are in)
         print("split exchange, object 0 (cycles relative to the first part's publish start of the round):")
         for rnd in range(16):
             start = [xt[(0 * 16 + rnd) * 16 + p] for p in range(parts)]

@@ -78,7 +78,7 @@ def main():
                 kernel = ""
                 if "get_step_kernel" in hip._fn:
                     nb = C.create_string_buffer(64)
-                    hip.call("get_step_kernel", nb, 64)
+                    hip.call("get_step_variant" if "get_step_variant" in hip._fn else "get_step_kernel", nb, 64)
                     kernel = nb.value.decode()
                 poses = np.zeros((n, 16), np.float32)
                 hip.call("bodies_get_poses", poses.ctypes.data_as(C.POINTER(C.c_float)), n)

@@ -18,7 +18,8 @@ inputs, joints, gt = bench_chain.chain_inputs(scenes, syn, 8, 8, 2)
 start_root = syn.perturb_pose(gt[0][0][0], np.random.default_rng(5), rot_deg=0.5, trans=0.001)
 ch = bench_chain.Chain(hip, host, syn, inputs, joints, start_root, gt[0][1] + 0.01, range(8))
 ch.upload(inputs, 0); ch.tracker.StartModalities(0)
-buf = (C.c_ulonglong * 32)()
+hip.lib.m3t_hip_debug_phase_rows.restype = C.c_int
+buf = (C.c_ulonglong * hip.lib.m3t_hip_debug_phase_rows())()  # M3T_PHASE_ROWS of the library
 for k in range(1, 4):
     ch.upload(inputs, k); ch.tracker.ExecuteTrackingStep(k)
 f(hip.ctx, buf, 1)
