@@ -191,6 +191,19 @@ class DataPoint(C.Structure):
                 ("valid", C.c_int), ("model_point_index", C.c_int)]
 
 
+class BodyJudgement(C.Structure):
+    """m3t_body_judgement: one body's row entry of m3t_hip_judge_bodies"""
+    _fields_ = [("translation_error", C.c_float), ("rotation_error", C.c_float), ("rotation_cosine", C.c_float),
+                ("tracking_success", C.c_float), ("add_error", C.c_float), ("adds_error", C.c_float),
+                ("was_reset", C.c_int32), ("reserved", C.c_int32)]
+
+
+BODY_JUDGEMENT_DTYPE = np.dtype([
+    ("translation_error", np.float32), ("rotation_error", np.float32), ("rotation_cosine", np.float32),
+    ("tracking_success", np.float32), ("add_error", np.float32), ("adds_error", np.float32),
+    ("was_reset", np.int32), ("reserved", np.int32)])
+assert BODY_JUDGEMENT_DTYPE.itemsize == C.sizeof(BodyJudgement) == 32
+
 DATA_LINE_DTYPE = np.dtype([
     ("center_f_body", np.float32, 3), ("center_u", np.float32), ("center_v", np.float32),
     ("normal_u", np.float32), ("normal_v", np.float32), ("delta_r", np.float32),
@@ -325,6 +338,12 @@ _HIP_ONLY = {
     "debug_log_checksum": [C.c_uint, C.c_uint, C.POINTER(C.c_ulonglong)],
     "set_object_split": [C.c_int],
     "reset_bodies": [c_int_p, c_float_p, C.c_int, C.c_int],
+    "judge_create": [c_int_p, C.c_int, C.c_int, c_int_p],
+    "judge_set_thresholds": [C.c_int, C.c_float, C.c_float],
+    "judge_set_vertices": [C.c_int, C.c_int, c_float_p, C.c_int],
+    "judge_bodies": [C.c_int, c_float_p, C.c_int, c_int_p],
+    "judge_read": [C.c_int, C.c_int, C.c_int, C.c_void_p],
+    "judge_clear": [C.c_int],
 }
 
 

@@ -23,6 +23,7 @@
 #include "m3t_device.h"
 #include "m3t_view_rows.h"
 #include "m3t_kernels.hip"
+#include "m3t_judge.hip"
 #include "m3t_compact.hip"
 #include "m3t_render.hip"
 #include "m3t_modelgen.hip"
@@ -167,6 +168,35 @@ struct Optimizer {
   std::vector<int> order;  // global link ids, depth first (parents before children)
   int dof = 0, n_rows = 0;
   size_t partial_offset = 0;
+};
+
+struct Judge {  // m3t_hip_judge_*: the evaluators' judgement of a list of bodies, rows of results in mapped host memory
+  static constexpr int kStage = 4;
+  std::vector<int> body_ids;
+  int n_rows_max = 0, n_rows = 0;
+  float thr_t = 0.05f, thr_r = 5.0f * 3.14159265358979323846f / 180.0f;  // rbot_evaluator.h:192-193
+  std::vector<int> n_vertices;
+  std::vector<std::unique_ptr<DevMem>> vertices;  // per listed body: float4, padded to a multiple of 4
+  DevMem d_bodies, d_parts, d_flags, d_partial;
+  int n_parts = 0, queries_per_thread = 1;
+  bool any_split = false;
+  m3t_body_judgement* rows_host = nullptr;  // [n_rows_max][n_bodies], written by the kernels in place
+  m3t_body_judgement* rows_dev = nullptr;
+  std::vector<hipEvent_t> row_done;         // per row: behind the launches of its call
+  // the ground-truth poses and the region-modality lists of a call, read in place by its launches
+  void* stage[kStage] = {nullptr};
+  size_t stage_bytes[kStage] = {0};
+  hipEvent_t stage_done[kStage] = {nullptr};
+  int stage_next = 0;
+  ~Judge() {
+    if (rows_host) (void)hipHostFree(rows_host);
+    for (auto& e : row_done)
+      if (e) (void)hipEventDestroy(e);
+    for (int i = 0; i < kStage; ++i) {
+      if (stage[i]) (void)hipHostFree(stage[i]);
+      if (stage_done[i]) (void)hipEventDestroy(stage_done[i]);
+    }
+  }
 };
 
 }  // namespace
@@ -329,6 +359,7 @@ struct m3t_hip_context {
   size_t reset_stage_bytes[kResetStage] = {0};
   hipEvent_t reset_stage_done[kResetStage] = {nullptr};
   int reset_stage_next = 0;
+  std::vector<std::unique_ptr<Judge>> judges;  // m3t_hip_judge_create
   // asynchronous ingest: frame copies run on their own stream beside the tracking kernels
   static constexpr int kStepEvents = 16;
   static constexpr int kCopyStreams = 4;  // cameras are spread round-robin: per-copy DMA latencies overlap
@@ -1551,6 +1582,8 @@ int UploadTables(Ctx* ctx) {
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(region_histogram_kernel),
                                hipFuncAttributeMaxDynamicSharedMemorySize, int(ctx->lds_hist)));
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(region_histogram_list_kernel),
+                               hipFuncAttributeMaxDynamicSharedMemorySize, int(ctx->lds_hist)));
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(region_histogram_flagged_kernel),
                                hipFuncAttributeMaxDynamicSharedMemorySize, int(ctx->lds_hist)));
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(depth_correspondence_kernel),
                                hipFuncAttributeMaxDynamicSharedMemorySize, int(ctx->lds_depth)));
@@ -3810,6 +3843,248 @@ int m3t_hip_reset_bodies(m3t_hip_context* ctx, const int* body_ids, const float*
     for (int c : cameras) ctx->cameras[c]->last_read_step[ctx->cameras[c]->current] = ctx->step_counter;
     ++ctx->step_counter;
   }
+  return M3T_OK;
+}
+// ---- the evaluators' judgement on the device (m3t_judge.hip) ---------------------------------------------------------
+}  // extern "C"
+namespace {
+// The launch shape of a judge: which workgroup searches which query range of which body.  Follows the batch: one query
+// per thread while that leaves no more than a few workgroups per CU, four per thread beyond.  (Create / set_vertices
+// only: waits for the stream, since earlier calls may still read the tables.)
+int BuildJudgeTables(Ctx* ctx, Judge* j) {
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  const int n = int(j->body_ids.size());
+  long chunks = 0;
+  for (int v : j->n_vertices) chunks += std::max(1, (v + M3T_JUDGE_SPLIT_QUERIES - 1) / M3T_JUDGE_SPLIT_QUERIES);
+  j->queries_per_thread = chunks > 4L * std::max(1, ctx->prop.multiProcessorCount) ? 4 : 1;
+  const int q = j->queries_per_thread * M3T_JUDGE_THREADS;
+  std::vector<JudgeBodyDev> bodies(static_cast<size_t>(n));
+  std::vector<JudgePartDev> parts;
+  j->any_split = false;
+  for (int i = 0; i < n; ++i) {
+    JudgeBodyDev& b = bodies[size_t(i)];
+    b.vertices = j->vertices[size_t(i)] ? j->vertices[size_t(i)]->as<float4>() : nullptr;
+    b.body = j->body_ids[size_t(i)];
+    b.n_vertices = j->n_vertices[size_t(i)];
+    b.first_part = int(parts.size());
+    b.n_parts = std::max(1, (b.n_vertices + q - 1) / q);
+    j->any_split = j->any_split || b.n_parts > 1;
+    for (int p = 0; p < b.n_parts; ++p) parts.push_back(JudgePartDev{i, p});
+  }
+  j->n_parts = int(parts.size());
+  HIPCHK(j->d_bodies.alloc(bodies.size() * sizeof(JudgeBodyDev)));
+  HIPCHK(j->d_parts.alloc(parts.size() * sizeof(JudgePartDev)));
+  HIPCHK(j->d_partial.alloc(parts.size() * 2 * sizeof(double)));
+  HIPCHK(j->d_flags.alloc(size_t(n) * sizeof(int)));
+  HIPCHK(hipMemcpy(j->d_bodies.p, bodies.data(), bodies.size() * sizeof(JudgeBodyDev), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(j->d_parts.p, parts.data(), parts.size() * sizeof(JudgePartDev), hipMemcpyHostToDevice));
+  HIPCHK(hipMemset(j->d_flags.p, 0, size_t(n) * sizeof(int)));
+  return M3T_OK;
+}
+}  // namespace
+extern "C" {
+
+int m3t_hip_judge_create(m3t_hip_context* ctx, const int* body_ids, int n_bodies, int n_rows_max, int* judge) {
+  CHECK_CTX();
+  REQUIRE(body_ids && judge && n_bodies >= 1 && n_rows_max >= 1, M3T_ERR_INVALID_ARGUMENT,
+          "judge_create: needs body ids, at least one body and one row");
+  REQUIRE(size_t(n_bodies) * size_t(n_rows_max) <= (size_t(1) << 23), M3T_ERR_INVALID_ARGUMENT,
+          "judge_create: more than 2^23 results (n_bodies x n_rows_max)");
+  const int n_all = int(ctx->body_poses.size() / 16);
+  std::vector<char> listed(size_t(n_all), 0);
+  for (int i = 0; i < n_bodies; ++i) {
+    REQUIRE(body_ids[i] >= 0 && body_ids[i] < n_all, M3T_ERR_INVALID_ARGUMENT, "judge_create: bad body id");
+    REQUIRE(!listed[body_ids[i]], M3T_ERR_INVALID_ARGUMENT, "judge_create: a body id is listed twice");
+    listed[body_ids[i]] = 1;
+  }
+  HIPCHK(hipSetDevice(ctx->device));
+  auto j = std::make_unique<Judge>();
+  j->body_ids.assign(body_ids, body_ids + n_bodies);
+  j->n_rows_max = n_rows_max;
+  j->n_vertices.assign(size_t(n_bodies), 0);
+  j->vertices.resize(size_t(n_bodies));
+  j->row_done.assign(size_t(n_rows_max), nullptr);
+  const size_t bytes = size_t(n_bodies) * size_t(n_rows_max) * sizeof(m3t_body_judgement);
+  HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&j->rows_host), bytes, hipHostMallocMapped));
+  std::memset(j->rows_host, 0, bytes);
+  HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&j->rows_dev), j->rows_host, 0));
+  int r = BuildJudgeTables(ctx, j.get());
+  if (r) return r;
+  ctx->judges.push_back(std::move(j));
+  *judge = int(ctx->judges.size()) - 1;
+  return M3T_OK;
+}
+int m3t_hip_judge_set_thresholds(m3t_hip_context* ctx, int judge, float translation_error_threshold,
+                                 float rotation_error_threshold) {
+  CHECK_CTX();
+  REQUIRE(judge >= 0 && judge < int(ctx->judges.size()), M3T_ERR_INVALID_ARGUMENT, "judge_set_thresholds: bad judge id");
+  ctx->judges[size_t(judge)]->thr_t = translation_error_threshold;
+  ctx->judges[size_t(judge)]->thr_r = rotation_error_threshold;
+  return M3T_OK;
+}
+int m3t_hip_judge_set_vertices(m3t_hip_context* ctx, int judge, int index, const float* xyz, int n_vertices) {
+  CHECK_CTX();
+  REQUIRE(judge >= 0 && judge < int(ctx->judges.size()), M3T_ERR_INVALID_ARGUMENT, "judge_set_vertices: bad judge id");
+  Judge* j = ctx->judges[size_t(judge)].get();
+  REQUIRE(index >= 0 && index < int(j->body_ids.size()), M3T_ERR_INVALID_ARGUMENT, "judge_set_vertices: bad body index");
+  REQUIRE(xyz && n_vertices >= 1 && n_vertices <= (1 << 18), M3T_ERR_INVALID_ARGUMENT,
+          "judge_set_vertices: 1 to 2^18 vertices");
+  HIPCHK(hipSetDevice(ctx->device));
+  const size_t n_padded = (size_t(n_vertices) + 3) / 4 * 4;
+  std::vector<float> padded(n_padded * 4, 0.0f);
+  for (size_t i = 0; i < n_padded; ++i) {
+    const float* v = xyz + 3 * (i < size_t(n_vertices) ? i : 0);  // a copy of vertex 0 never changes a minimum
+    padded[4 * i] = v[0];
+    padded[4 * i + 1] = v[1];
+    padded[4 * i + 2] = v[2];
+  }
+  HIPCHK(hipStreamSynchronize(ctx->stream));  // earlier calls may still search the old vertices
+  auto mem = std::make_unique<DevMem>();
+  HIPCHK(mem->alloc(padded.size() * 4));
+  HIPCHK(hipMemcpy(mem->p, padded.data(), padded.size() * 4, hipMemcpyHostToDevice));
+  j->vertices[size_t(index)] = std::move(mem);
+  j->n_vertices[size_t(index)] = n_vertices;
+  return BuildJudgeTables(ctx, j);
+}
+// CalculatePoseResults of the listed bodies against these ground-truth poses into the next row and, with
+// reset_iteration >= 0, ResetBody of those the device finds lost -- enqueued behind whatever the stream holds (m3t_hip.h).
+int m3t_hip_judge_bodies(m3t_hip_context* ctx, int judge, const float* gt_body2world_poses, int reset_iteration, int* row) {
+  CHECK_CTX();
+  REQUIRE(judge >= 0 && judge < int(ctx->judges.size()), M3T_ERR_INVALID_ARGUMENT, "judge_bodies: bad judge id");
+  Judge* j = ctx->judges[size_t(judge)].get();
+  REQUIRE(gt_body2world_poses, M3T_ERR_INVALID_ARGUMENT, "judge_bodies: null ground-truth poses");
+  REQUIRE(j->n_rows < j->n_rows_max, M3T_ERR_INVALID_ARGUMENT,
+          "judge_bodies: the row table is full (judge_read, then judge_clear)");
+  const int n = int(j->body_ids.size());
+  const int n_all = int(ctx->body_poses.size() / 16);
+  const bool reset = reset_iteration >= 0;
+  std::vector<int> region_ids, region_body_index, region_first(size_t(n) + 1, 0), cameras;
+  if (reset) {  // the host cannot follow a reset the device decides: only what needs no host mirror
+    std::vector<int> index_of(size_t(n_all), -1);
+    for (int i = 0; i < n; ++i) index_of[size_t(j->body_ids[size_t(i)])] = i;
+    for (auto& l : ctx->links)
+      REQUIRE(l.body < 0 || index_of[size_t(l.body)] < 0 || (l.parent < 0 && l.children.empty()), M3T_ERR_UNSUPPORTED,
+              "judge_bodies: a listed body belongs to a structure of more than one link (judge with "
+              "reset_iteration < 0 and reset the structure from the host)");
+    std::vector<std::vector<int>> of_body(static_cast<size_t>(n));
+    for (size_t i = 0; i < ctx->region_mods.size(); ++i) {
+      const RegionMod& m = *ctx->region_mods[i];
+      const int li = index_of[size_t(m.body)];
+      if (li < 0) continue;
+      REQUIRE(m.shared_histograms < 0, M3T_ERR_UNSUPPORTED,
+              "judge_bodies: a region modality of a listed body uses shared ColorHistograms (call start_modalities)");
+      REQUIRE(m.dev.first_iteration == reset_iteration, M3T_ERR_INVALID_ARGUMENT,
+              "judge_bodies: first_iteration of a listed body's region modality differs from reset_iteration (the "
+              "host could not follow a change the device decides; start_modalities(reset_iteration) first)");
+      REQUIRE(!(m.dev.model_occlusions && m.depth_renderer >= 0) && !(m.dev.use_region_checking && m.silhouette_renderer >= 0),
+              M3T_ERR_UNSUPPORTED,
+              "judge_bodies: a region modality of a listed body reads a start-modality renderer (judge with "
+              "reset_iteration < 0 and call reset_bodies)");
+      of_body[size_t(li)].push_back(int(i));
+      cameras.push_back(m.camera);
+      if (m.depth_camera >= 0) cameras.push_back(m.depth_camera);
+    }
+    for (auto& m : ctx->depth_mods)
+      if (index_of[size_t(m->body)] >= 0) cameras.push_back(m->camera);
+    for (int c : cameras)
+      REQUIRE(!ctx->cameras[c]->slot_is_roi[ctx->cameras[c]->current], M3T_ERR_UNSUPPORTED,
+              "judge_bodies: a frame slot the modalities read holds the trackers' rectangle only (ROI ingest); "
+              "upload the whole frame into it first (camera_upload_slot)");
+    for (int i = 0; i < n; ++i) {
+      for (int id : of_body[size_t(i)]) {
+        region_ids.push_back(id);
+        region_body_index.push_back(i);
+      }
+      region_first[size_t(i) + 1] = int(region_ids.size());
+    }
+  }
+  HIPCHK(hipSetDevice(ctx->device));
+  const bool untracked_before = ctx->untracked_launches;
+  if (reset && ctx->poses_dirty_host) ctx->roi_end_valid = false;
+  int r = Prepare(ctx, reset);  // (tables and poses that were waiting for their upload anyway)
+  if (r) return r;
+  ctx->untracked_launches = untracked_before;  // reads poses only, or is tracked by a step_done event below
+  // the call's arguments: [ground-truth poses][region modality ids][their listed body][first region of each body]
+  const size_t n_region = region_ids.size();
+  const size_t off_ints = size_t(n) * 64;
+  const size_t bytes = off_ints + (2 * n_region + size_t(n) + 1) * 4;
+  const int stage = j->stage_next;
+  j->stage_next = (stage + 1) % Judge::kStage;
+  if (!j->stage_done[stage]) HIPCHK(hipEventCreateWithFlags(&j->stage_done[stage], hipEventDisableTiming));
+  HIPCHK(hipEventSynchronize(j->stage_done[stage]));  // the call four judgements ago: normally long complete
+  if (j->stage_bytes[stage] < bytes) {
+    if (j->stage[stage]) HIPCHK(hipHostFree(j->stage[stage]));
+    j->stage[stage] = nullptr;
+    j->stage_bytes[stage] = 0;
+    HIPCHK(hipHostMalloc(&j->stage[stage], bytes * 2, hipHostMallocMapped));
+    j->stage_bytes[stage] = bytes * 2;
+  }
+  uint8_t* h = static_cast<uint8_t*>(j->stage[stage]);
+  std::memcpy(h, gt_body2world_poses, size_t(n) * 64);
+  int* h_ints = reinterpret_cast<int*>(h + off_ints);
+  if (n_region) {
+    std::memcpy(h_ints, region_ids.data(), n_region * 4);
+    std::memcpy(h_ints + n_region, region_body_index.data(), n_region * 4);
+  }
+  std::memcpy(h_ints + 2 * n_region, region_first.data(), (size_t(n) + 1) * 4);
+  void* dev = nullptr;
+  HIPCHK(hipHostGetDevicePointer(&dev, j->stage[stage], 0));
+  const float* d_gt = static_cast<const float*>(dev);
+  const int* d_region_ids = reinterpret_cast<const int*>(static_cast<const uint8_t*>(dev) + off_ints);
+  const int* d_region_body = d_region_ids + n_region;
+  const int* d_region_first = d_region_ids + 2 * n_region;
+  const int row_index = j->n_rows;
+  m3t_body_judgement* d_row = j->rows_dev + size_t(row_index) * size_t(n);
+  if (!j->row_done[size_t(row_index)])
+    HIPCHK(hipEventCreateWithFlags(&j->row_done[size_t(row_index)], hipEventDisableTiming));
+  hipLaunchKernelGGL(j->queries_per_thread == 4 ? judge_bodies_x4_kernel : judge_bodies_kernel, dim3(unsigned(j->n_parts)),
+                     dim3(M3T_JUDGE_THREADS), 0, ctx->stream, ctx->d_poses.as<float>(), j->d_bodies.as<JudgeBodyDev>(),
+                     j->d_parts.as<JudgePartDev>(), d_gt, j->thr_t, j->thr_r, reset_iteration,
+                     ctx->d_region.as<RegionModDev>(), d_region_ids, d_region_first, j->d_flags.as<int>(), d_row,
+                     j->d_partial.as<double>());
+  if (j->any_split)
+    hipLaunchKernelGGL(judge_finish_kernel, dim3(unsigned(n)), dim3(64), 0, ctx->stream, ctx->d_poses.as<float>(),
+                       j->d_bodies.as<JudgeBodyDev>(), d_gt, reset_iteration, ctx->d_region.as<RegionModDev>(),
+                       d_region_ids, d_region_first, j->d_flags.as<int>(), d_row, j->d_partial.as<double>());
+  if (n_region) {
+    ScopedKernelTimer timer(ctx, 1);
+    hipLaunchKernelGGL(region_histogram_flagged_kernel, dim3(unsigned(n_region)), dim3(M3T_BLOCK_THREADS), ctx->lds_hist,
+                       ctx->stream, ctx->d_region.as<RegionModDev>(), d_region_ids, d_region_body, j->d_flags.as<int>(),
+                       ctx->cams_active, ctx->d_poses.as<float>(), ctx->hist_counts_in_lds ? 1 : 0);
+  }
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(j->stage_done[stage], ctx->stream));
+  HIPCHK(hipEventRecord(j->row_done[size_t(row_index)], ctx->stream));
+  if (reset) {
+    ctx->roi_end_valid = false;  // the host's mirror does not vouch for these bodies' poses any more
+    if (ctx->async_ingest) {  // a later asynchronous upload into a slot these launches read waits for them
+      HIPCHK(hipEventRecord(ctx->step_done[ctx->step_counter % Ctx::kStepEvents], ctx->stream));
+      for (int c : cameras) ctx->cameras[c]->last_read_step[ctx->cameras[c]->current] = ctx->step_counter;
+      ++ctx->step_counter;
+    }
+  }
+  ++j->n_rows;
+  if (row) *row = row_index;
+  return M3T_OK;
+}
+int m3t_hip_judge_read(m3t_hip_context* ctx, int judge, int first_row, int n_rows, m3t_body_judgement* out) {
+  CHECK_CTX();
+  REQUIRE(judge >= 0 && judge < int(ctx->judges.size()), M3T_ERR_INVALID_ARGUMENT, "judge_read: bad judge id");
+  Judge* j = ctx->judges[size_t(judge)].get();
+  REQUIRE(first_row >= 0 && n_rows >= 0 && first_row <= j->n_rows && n_rows <= j->n_rows - first_row,
+          M3T_ERR_INVALID_ARGUMENT, "judge_read: rows that have not been judged");
+  if (n_rows == 0) return M3T_OK;
+  REQUIRE(out, M3T_ERR_INVALID_ARGUMENT, "judge_read: null output");
+  HIPCHK(hipSetDevice(ctx->device));
+  HIPCHK(hipEventSynchronize(j->row_done[size_t(first_row + n_rows - 1)]));  // rows complete in order
+  const size_t n = j->body_ids.size();
+  std::memcpy(out, j->rows_host + size_t(first_row) * n, size_t(n_rows) * n * sizeof(m3t_body_judgement));
+  return M3T_OK;
+}
+int m3t_hip_judge_clear(m3t_hip_context* ctx, int judge) {
+  CHECK_CTX();
+  REQUIRE(judge >= 0 && judge < int(ctx->judges.size()), M3T_ERR_INVALID_ARGUMENT, "judge_clear: bad judge id");
+  ctx->judges[size_t(judge)]->n_rows = 0;
   return M3T_OK;
 }
 int m3t_hip_calculate_correspondences(m3t_hip_context* ctx, int iteration, int corr_iteration) {

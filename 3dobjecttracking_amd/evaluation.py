@@ -81,19 +81,41 @@ def evaluate_rbot_sequence(tracker, body, poses_gt, load_image, n_frames=None, r
     return frames, avg
 
 
-def evaluate_rbot_sequences(tracker, bodies, poses_gt_per_body, load_images, n_frames):
+def evaluate_rbot_sequences(tracker, bodies, poses_gt_per_body, load_images, n_frames, judge_on_device=False):
     """The loop of evaluate_rbot_sequence for N independent bodies in ONE context (HIP library): every body starts on
     image 0 at its own ground truth, cycle i tracks image i + 1 of all of them in one step, every body is judged
     against its own ground truth, and the lost ones -- those alone -- are reset with one Tracker.ResetBodies call
     (ResetBody :334-342 per body: its pose, StartModality(0, 0) of its modalities), so that each body's results are
     those of a tracker of its own.  `load_images(k)` makes image k current in every body's camera.
-    Returns (per-body lists of per-frame results, per-body averages); complete_cycle is the time of the batch's step."""
+    Returns (per-body lists of per-frame results, per-body averages); complete_cycle is the time of the batch's step.
+    judge_on_device (HIP library): the judgement and the reset are the device's (Tracker.CreateJudge, judge(gt, 0)
+    behind every step): the loop makes no Sync() and reads no pose per frame, and the rows are read once after the last
+    frame.  complete_cycle is then the loop's wall time, the final read included, divided by its frames."""
     for body, poses_gt in zip(bodies, poses_gt_per_body):
         body.set_body2world_pose(poses_gt[0])
     load_images(0)
     if not tracker.StartModalities(0):
         raise RuntimeError("StartModalities failed")
     frames = [[] for _ in bodies]
+    keys = ("translation_error", "rotation_error", "tracking_success", "complete_cycle")
+    if judge_on_device:
+        judge = tracker.CreateJudge(bodies, max(1, n_frames))
+        t0 = time.perf_counter()
+        for i in range(n_frames):
+            load_images(i + 1)
+            if not tracker.ExecuteTrackingStep(i):
+                raise RuntimeError("tracking step %d failed" % i)
+            judge.judge([poses_gt[i + 1] for poses_gt in poses_gt_per_body], 0)
+        rows = judge.read(0, n_frames)
+        dt = (time.perf_counter() - t0) * 1e6 / max(1, n_frames)
+        for i in range(n_frames):
+            for j in range(len(bodies)):
+                r = rows[i, j]
+                frames[j].append(dict(frame_index=i, translation_error=float(r["translation_error"]),
+                                      rotation_error=float(r["rotation_error"]),
+                                      tracking_success=float(r["tracking_success"]), complete_cycle=dt))
+        averages = [{k: float(np.mean([f[k] for f in fs])) for k in keys} for fs in frames]
+        return frames, averages
     for i in range(n_frames):
         load_images(i + 1)
         t0 = time.perf_counter()
@@ -110,7 +132,6 @@ def evaluate_rbot_sequences(tracker, bodies, poses_gt_per_body, load_images, n_f
                 lost.append(j)
         if lost and not tracker.ResetBodies([bodies[j] for j in lost], [poses_gt_per_body[j][i + 1] for j in lost], 0):
             raise RuntimeError("ResetBodies failed")
-    keys = ("translation_error", "rotation_error", "tracking_success", "complete_cycle")
     averages = [{k: float(np.mean([f[k] for f in fs])) for k in keys} for fs in frames]
     return frames, averages
 
@@ -198,7 +219,10 @@ class YCBBodyEvaluation:
         return add, adds
 
     def result(self, body2world_pose, gt_body2world_pose):
-        add, adds = self.errors(body2world_pose, gt_body2world_pose)
+        return self.result_of_errors(*self.errors(body2world_pose, gt_body2world_pose))
+
+    def result_of_errors(self, add, adds):
+        """errors, curves and AUC from ADD / ADD-S in metres (judged here or on the device)"""
         out = dict(add_error=add, adds_error=adds)
         for key, err in (("add", add), ("adds", adds)):
             curve = np.ones(K_N_CURVE_VALUES, F)
@@ -211,26 +235,51 @@ class YCBBodyEvaluation:
         return out
 
 
-def evaluate_ycb_sequence(tracker, bodies, evaluations, gt_body2world_poses, keyframes, update_cameras):
+def evaluate_ycb_sequence(tracker, bodies, evaluations, gt_body2world_poses, keyframes, update_cameras,
+                          judge_on_device=False):
     """YCBEvaluator::EvaluateRunConfiguration without refinement (ycb_evaluator.cpp:333-372): bodies start at
     the ground truth of the first keyframe, StartModalities once, then one tracking step per keyframe and the
-    ADD / ADD-S results of every evaluated body.  bodies / evaluations / gt poses are dicts by body name."""
+    ADD / ADD-S results of every evaluated body.  bodies / evaluations / gt poses are dicts by body name.
+    judge_on_device (HIP library): ADD / ADD-S of the evaluated bodies are formed on the device over the evaluations'
+    vertices (Tracker.CreateJudge, judge(gt, -1) behind every step); the loop makes no Sync() and reads no pose per
+    frame, the rows are read once after the last keyframe and the curves and AUC are formed from them by
+    YCBBodyEvaluation.result's code.  complete_cycle is then the loop's wall time, the final read included, divided by
+    its keyframes."""
     for name, body in bodies.items():
         body.set_body2world_pose(gt_body2world_poses[name][0])
     update_cameras(keyframes[0])
     if not tracker.StartModalities(0):
         raise RuntimeError("StartModalities failed")
     results = {name: [] for name in evaluations}
-    for i, frame in enumerate(keyframes):
-        update_cameras(frame)
+    if judge_on_device:
+        names = list(evaluations)
+        judge = tracker.CreateJudge([bodies[name] for name in names], max(1, len(keyframes)))
+        for j, name in enumerate(names):
+            judge.set_vertices(j, evaluations[name].vertices)
         t0 = time.perf_counter()
-        if not (tracker.ExecuteTrackingStep(i) and tracker.Sync()):
-            raise RuntimeError("tracking step %d failed" % i)
-        dt = (time.perf_counter() - t0) * 1e6
-        for name, ev in evaluations.items():
-            r = ev.result(bodies[name].body2world_pose(), gt_body2world_poses[name][i])
-            r.update(frame_index=i, complete_cycle=dt)
-            results[name].append(r)
+        for i, frame in enumerate(keyframes):
+            update_cameras(frame)
+            if not tracker.ExecuteTrackingStep(i):
+                raise RuntimeError("tracking step %d failed" % i)
+            judge.judge([gt_body2world_poses[name][i] for name in names], -1)
+        rows = judge.read(0, len(keyframes))
+        dt = (time.perf_counter() - t0) * 1e6 / max(1, len(keyframes))
+        for i in range(len(keyframes)):
+            for j, name in enumerate(names):
+                r = evaluations[name].result_of_errors(float(rows[i, j]["add_error"]), float(rows[i, j]["adds_error"]))
+                r.update(frame_index=i, complete_cycle=dt)
+                results[name].append(r)
+    else:
+        for i, frame in enumerate(keyframes):
+            update_cameras(frame)
+            t0 = time.perf_counter()
+            if not (tracker.ExecuteTrackingStep(i) and tracker.Sync()):
+                raise RuntimeError("tracking step %d failed" % i)
+            dt = (time.perf_counter() - t0) * 1e6
+            for name, ev in evaluations.items():
+                r = ev.result(bodies[name].body2world_pose(), gt_body2world_poses[name][i])
+                r.update(frame_index=i, complete_cycle=dt)
+                results[name].append(r)
     average = {}
     for name, rs in results.items():
         average[name] = dict(add_auc=float(np.mean([r["add_auc"] for r in rs])),
@@ -261,7 +310,7 @@ def evaluate_rbot_dataset(open_context, dataset_directory, external_directory, b
                           sequence_names=RBOT_SEQUENCE_NAMES, n_frames=1000, region_parameters=None,
                           model_parameters=None, tikhonov_parameter_rotation=1000.0,
                           tikhonov_parameter_translation=30000.0, n_corr_iterations=7, n_update_iterations=2,
-                          report=None, shard=(0, 1), batch=1):
+                          report=None, shard=(0, 1), batch=1, judge_on_device=False):
     """RBOTEvaluator::SetUp + Evaluate for the region modality on the un-modelled sequences: for every (sequence,
     body) a tracker on `dataset/<body>/frames/<sequence>NNNN.png`, started at `dataset/poses_first.txt`, reset on
     loss, scored with the 5 cm / 5 degree criterion.  Bodies are `dataset/<body>/<body>.obj` in millimetres
@@ -274,16 +323,19 @@ def evaluate_rbot_dataset(open_context, dataset_directory, external_directory, b
     dictionaries).
     batch > 1 (HIP library): up to `batch` of this process's runs share one context -- each with its own body, model,
     loader camera and optimizer -- and go through evaluate_rbot_sequences, which resets the lost bodies alone; the
-    results are those of batch = 1."""
+    results are those of batch = 1.
+    judge_on_device (HIP library): the batched loop with the judgement and the reset on the device
+    (evaluate_rbot_sequences; with batch = 1 a batch of one)."""
     import os
 
     from . import config as cfg
     from . import generator, host
-    if batch > 1:
+    if batch > 1 or judge_on_device:
         return _evaluate_rbot_dataset_batched(open_context, dataset_directory, external_directory, body_names,
                                               sequence_names, n_frames, region_parameters, model_parameters,
                                               tikhonov_parameter_rotation, tikhonov_parameter_translation,
-                                              n_corr_iterations, n_update_iterations, report, shard, batch)
+                                              n_corr_iterations, n_update_iterations, report, shard, max(1, batch),
+                                              judge_on_device)
     poses_first = read_poses_rbot(os.path.join(dataset_directory, "poses_first.txt"), n_frames)
     region_parameters = dict(RBOT_REGION_PARAMETERS, **(region_parameters or {}))
     model_parameters = dict(RBOT_MODEL_PARAMETERS, **(model_parameters or {}))
@@ -325,7 +377,7 @@ def evaluate_rbot_dataset(open_context, dataset_directory, external_directory, b
 def _evaluate_rbot_dataset_batched(open_context, dataset_directory, external_directory, body_names, sequence_names,
                                    n_frames, region_parameters, model_parameters, tikhonov_parameter_rotation,
                                    tikhonov_parameter_translation, n_corr_iterations, n_update_iterations, report,
-                                   shard, batch):
+                                   shard, batch, judge_on_device=False):
     """evaluate_rbot_dataset with up to `batch` runs per context (same runs, same order, same results)"""
     import os
 
@@ -366,7 +418,8 @@ def _evaluate_rbot_dataset_batched(open_context, dataset_directory, external_dir
                 if not camera.UpdateImage():
                     raise RuntimeError("Could not read image from %s" % camera.image_path())
 
-        _, averages = evaluate_rbot_sequences(tracker, bodies, [poses_first] * len(chunk), load_images, n_frames)
+        _, averages = evaluate_rbot_sequences(tracker, bodies, [poses_first] * len(chunk), load_images, n_frames,
+                                              judge_on_device=judge_on_device)
         for (sequence, name), average in zip(chunk, averages):
             results[(sequence, name)] = average
             if report is not None:
@@ -438,14 +491,15 @@ def evaluate_ycb_dataset(open_context, dataset_directory, external_directory, se
                          use_matlab_gt_poses=True, n_vertices_evaluation=1000, region_parameters=None,
                          depth_parameters=None, model_parameters=None, tikhonov_parameter_rotation=1000.0,
                          tikhonov_parameter_translation=30000.0, n_corr_iterations=4, n_update_iterations=2,
-                         report=None, shard=(0, 1)):
+                         report=None, shard=(0, 1), judge_on_device=False):
     """YCBEvaluator::SetUp + Evaluate with the region and the depth modality, measured occlusions, one run per
     (sequence, body present in it) (CreateRunConfigurations :1006-1022): bodies `dataset/models/<body>/textured.obj`
     in metres, frames `dataset/data/<sequence>/NNNNNN-{color,depth}.png` (depth scale 1e-4), keyframes from
     `dataset/image_sets/keyframe.txt`, ground truth from `external/poses/ground_truth/<sequence>_<body>.txt` (or the
     dataset's own `poses/<body>.txt`), models under `external/models/`.  Returns {(sequence, body): average} and
     the averages over all frames of all runs (CalculateAverageResult).  shard = (rank, world): every world-th run
-    (see evaluate_rbot_dataset); the overall averages then cover this process's runs."""
+    (see evaluate_rbot_dataset); the overall averages then cover this process's runs.
+    judge_on_device (HIP library): ADD / ADD-S on the device (evaluate_ycb_sequence)."""
     import os
 
     from . import config as cfg
@@ -505,7 +559,7 @@ def evaluate_ycb_dataset(open_context, dataset_directory, external_directory, se
 
         evaluation = YCBBodyEvaluation(body.vertices, n_vertices_evaluation)
         per_frame, average = evaluate_ycb_sequence(tracker, {name: body}, {name: evaluation}, {name: gt}, keyframes,
-                                                   update_cameras)
+                                                   update_cameras, judge_on_device=judge_on_device)
         results[(sequence, name)] = average[name]
         frame_results += per_frame[name]
         if report is not None:

@@ -83,6 +83,10 @@ class Tracker:
             raise M3TError(-3, "%sreset_bodies: this entry point exists in the HIP library only" % self.api.prefix)
         return self._step("reset_bodies", iptr(ids), fptr(flat) if flat is not None else None, len(ids), iteration)
 
+    def CreateJudge(self, bodies, n_rows_max):
+        """the evaluators' judgement of `bodies` on the device (HIP library only): see Judge"""
+        return Judge(self.api, bodies, n_rows_max)
+
     # asynchronous ingest (HIP library only)
     def register_host_buffer(self, array):
         """page-lock a caller-owned frame buffer so that asynchronous uploads overlap the tracking kernels"""
@@ -106,6 +110,60 @@ class Tracker:
 
     def Sync(self):
         return self._step("sync")
+
+
+class Judge:
+    """m3t_hip_judge_*: RBOTEvaluator::CalculatePoseResults / YCBEvaluator::CalculatePoseResults of a list of bodies on
+    the device, with ResetBody of the bodies the device finds lost (reset_iteration >= 0).  `judge` is enqueued behind
+    the step like Tracker.ResetBodies and returns the index of the row it fills; nothing waits until `read`."""
+
+    def __init__(self, api, bodies, n_rows_max):
+        if "judge_create" not in api._fn:
+            raise M3TError(-3, "%sjudge_create: this entry point exists in the HIP library only" % api.prefix)
+        self.api = api
+        self.bodies = list(bodies)
+        self.n_rows_max = int(n_rows_max)
+        ids = np.asarray([b.id for b in self.bodies], np.int32)
+        out = C.c_int(-1)
+        api.call("judge_create", iptr(ids), len(ids), self.n_rows_max, C.byref(out))
+        self.id = out.value
+        self._gt = np.zeros(16 * len(ids), np.float32)
+
+    def set_thresholds(self, translation_error_threshold=0.05, rotation_error_threshold=5.0 * np.pi / 180.0):
+        self.api.call("judge_set_thresholds", self.id, float(translation_error_threshold),
+                      float(rotation_error_threshold))
+
+    def set_vertices(self, body, vertices):
+        """the (reduced) evaluation vertices of `body` (a listed Body or its index in the list): ADD / ADD-S"""
+        index = body if isinstance(body, (int, np.integer)) else [b.id for b in self.bodies].index(body.id)
+        v = np.ascontiguousarray(vertices, np.float32).reshape(-1, 3)
+        self.api.call("judge_set_vertices", self.id, int(index), fptr(v), len(v))
+
+    def raw_judge(self, gt_poses, reset_iteration=-1):
+        """(status, row) without raising"""
+        assert len(gt_poses) == len(self.bodies)
+        g = self._gt.reshape(-1, 4, 4)
+        for i, p in enumerate(gt_poses):  # column-major
+            g[i] = np.asarray(p, np.float32).reshape(4, 4).T
+        row = C.c_int(-1)
+        rc = self.api.raw("judge_bodies", self.id, fptr(self._gt), int(reset_iteration), C.byref(row))
+        return rc, row.value
+
+    def judge(self, gt_poses, reset_iteration=-1):
+        rc, row = self.raw_judge(gt_poses, reset_iteration)
+        if rc < 0:
+            raise M3TError(rc, self.api.last_error())
+        return row
+
+    def read(self, first_row, n_rows):
+        """rows [first_row, first_row + n_rows) as a structured array [n_rows][n_bodies] (BODY_JUDGEMENT_DTYPE);
+        waits for the last of them only"""
+        out = np.zeros((n_rows, len(self.bodies)), _capi.BODY_JUDGEMENT_DTYPE)
+        self.api.call("judge_read", self.id, int(first_row), int(n_rows), out.ctypes.data_as(C.c_void_p))
+        return out
+
+    def clear(self):
+        self.api.call("judge_clear", self.id)
 
 
 class Body:

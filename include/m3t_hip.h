@@ -309,6 +309,43 @@ int m3t_hip_start_modalities(m3t_hip_context*, int iteration);                  
  * A body without modalities only gets its pose. */
 int m3t_hip_reset_bodies(m3t_hip_context*, const int* body_ids, const float* body2world_poses /* n x 16, or NULL */,
                          int n, int iteration);
+/* The evaluators' judgement on the device.  A judge holds a list of bodies, their evaluation vertices (optional) and a
+ * table of n_rows_max result rows of n_bodies m3t_body_judgement each.
+ * judge_bodies judges every listed body against its ground-truth pose (n_bodies x 16, column-major) into the next row:
+ *   - translation_error, rotation_error, tracking_success: RBOTEvaluator::CalculatePoseResults
+ *     (examples/rbot_evaluator.cpp:416-433) in f32, sums left to right, acos in double; thresholds
+ *     judge_set_thresholds (defaults 0.05f, 5 degrees: rbot_evaluator.h:192-193); a NaN rotation error is "not lost";
+ *   - add_error, adds_error for a body with vertices (judge_set_vertices, the reduced vertices of
+ *     YCBEvaluator::GenderateReducedVertices): YCBEvaluator::CalculatePoseResults (examples/ycb_evaluator.cpp:803-848),
+ *     delta = body2world^-1 * gt formed in f64 and rounded to f32, the nearest vertex by exhaustive search (the minimum
+ *     a k-d tree returns), sums in f64 in a fixed order: two calls on the same inputs return the same bits.
+ * reset_iteration >= 0: every body found lost is reset as m3t_hip_reset_bodies(ids, gt poses, n, reset_iteration) resets
+ * a list -- its pose becomes its ground truth, first_iteration of its region modalities becomes reset_iteration,
+ * StartModality initialises their histograms -- and its was_reset is 1; every other body keeps its pose, histograms,
+ * first_iteration, line / point state and g/H bit for bit.  reset_iteration < 0: nothing but the row is written.
+ * The call is enqueued on the context's stream behind whatever it holds, like reset_bodies: it reads no pose back, does
+ * not wait for the stream and uploads no table; the ground-truth poses cross through a small ring of mapped host blocks
+ * (the call may wait for the judgement four calls earlier).  A whole evaluated sequence can be queued without a wait
+ * and read at its end.  Arguments are checked before anything changes:
+ *   M3T_ERR_INVALID_ARGUMENT  bad ids; the row table is full (nothing is enqueued, no row consumed: judge_read, then
+ *                             judge_clear); with a reset: a listed body's region modality whose first_iteration differs
+ *                             from reset_iteration (the host cannot follow a change the device decides; the evaluators
+ *                             pass 0 after start_modalities(0))
+ *   M3T_ERR_UNSUPPORTED       with a reset: the refusals of reset_bodies (a structure of more than one link, shared
+ *                             ColorHistograms, a frame slot that holds an ROI rectangle only), and a region modality
+ *                             that reads a start-modality renderer (model_occlusions / use_region_checking: judge with
+ *                             reset_iteration < 0 and call reset_bodies)
+ * After a resetting call the host's pose mirror does not vouch for these bodies (as after reset_bodies with poses).
+ * judge_read waits for the event of the last requested row only and copies rows [first_row, first_row + n_rows) to
+ * out[n_rows][n_bodies]; judge_clear starts the rows at 0 again.  judge_set_vertices (1 <= n <= 1 << 18 vertices of
+ * body_ids[index], xyz) and judge_create wait for the stream and upload; call them outside the frame loop. */
+int m3t_hip_judge_create(m3t_hip_context*, const int* body_ids, int n_bodies, int n_rows_max, int* judge);
+int m3t_hip_judge_set_thresholds(m3t_hip_context*, int judge, float translation_error_threshold,
+                                 float rotation_error_threshold);
+int m3t_hip_judge_set_vertices(m3t_hip_context*, int judge, int index, const float* xyz, int n_vertices);
+int m3t_hip_judge_bodies(m3t_hip_context*, int judge, const float* gt_body2world_poses, int reset_iteration, int* row);
+int m3t_hip_judge_read(m3t_hip_context*, int judge, int first_row, int n_rows, m3t_body_judgement* out);
+int m3t_hip_judge_clear(m3t_hip_context*, int judge);
 int m3t_hip_calculate_correspondences(m3t_hip_context*, int iteration, int corr_iteration); /* :447 */
 int m3t_hip_calculate_gradient_and_hessian(m3t_hip_context*, int iteration, int corr_iteration,
                                            int opt_iteration);                    /* :471 */

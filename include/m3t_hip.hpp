@@ -459,6 +459,44 @@ class Tracker {
                                          int(body_ids.size()), iteration));
   }
 
+  // The evaluators' judgement on the device (m3t_hip_judge_*): CalculatePoseResults of RBOTEvaluator / YCBEvaluator for
+  // a list of bodies, ResetBody of the bodies the device finds lost (reset_iteration >= 0).  Judge() is enqueued behind
+  // the step like ResetBodies and returns the row it fills (-1: refused); nothing waits until Read().
+  class Judge {
+   public:
+    Judge(ContextPtr c, const std::vector<const Body*>& bodies, int n_rows_max) : c_(std::move(c)), n_(bodies.size()) {
+      std::vector<int> body_ids;
+      for (const Body* body : bodies) body_ids.push_back(body->id());
+      c_->Check(m3t_hip_judge_create(c_->get(), body_ids.data(), int(body_ids.size()), n_rows_max, &id_), "Judge");
+    }
+    void SetThresholds(float translation_error_threshold, float rotation_error_threshold) {
+      c_->Check(m3t_hip_judge_set_thresholds(c_->get(), id_, translation_error_threshold, rotation_error_threshold), "Judge");
+    }
+    void SetVertices(int index, const std::vector<std::array<float, 3>>& vertices) {
+      c_->Check(m3t_hip_judge_set_vertices(c_->get(), id_, index, vertices.empty() ? nullptr : vertices[0].data(),
+                                           int(vertices.size())),
+                "Judge");
+    }
+    int JudgeBodies(const std::vector<Pose>& gt_body2world_poses, int reset_iteration = -1) {
+      int row = -1;
+      if (gt_body2world_poses.size() != n_) return -1;
+      return c_->Step(m3t_hip_judge_bodies(c_->get(), id_, gt_body2world_poses[0].data(), reset_iteration, &row)) ? row : -1;
+    }
+    std::vector<m3t_body_judgement> Read(int first_row, int n_rows) const {  // [n_rows][n_bodies]
+      std::vector<m3t_body_judgement> out(size_t(n_rows > 0 ? n_rows : 0) * n_);
+      c_->Check(m3t_hip_judge_read(c_->get(), id_, first_row, n_rows, out.data()), "Judge");
+      return out;
+    }
+    void Clear() { c_->Check(m3t_hip_judge_clear(c_->get(), id_), "Judge"); }
+    size_t n_bodies() const { return n_; }
+
+   private:
+    ContextPtr c_;
+    size_t n_;
+    int id_ = -1;
+  };
+  Judge CreateJudge(const std::vector<const Body*>& bodies, int n_rows_max) { return Judge(c_, bodies, n_rows_max); }
+
   // ---- the batch at once, and what has no counterpart in the reference (m3t_hip.h) ----
   // poses of the first n bodies in creation order, one copy each way
   void SetBodyPoses(const std::vector<Pose>& poses) {

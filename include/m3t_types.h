@@ -188,6 +188,18 @@ typedef struct m3t_data_point {
   int model_point_index;
 } m3t_data_point;
 
+/* One body's judgement by m3t_hip_judge_bodies: RBOTEvaluator::CalculatePoseResults (rbot_evaluator.cpp:416-433) and
+ * YCBEvaluator::CalculatePoseResults (ycb_evaluator.cpp:803-848).  32 bytes. */
+typedef struct m3t_body_judgement {
+  float translation_error;   /* m */
+  float rotation_error;      /* rad; NaN where acos() is, as in the reference */
+  float rotation_cosine;     /* (trace(R^T R_gt) - 1) / 2, the acos argument */
+  float tracking_success;    /* 1 / 0 */
+  float add_error, adds_error; /* m; 0 for a body without evaluation vertices */
+  int32_t was_reset;         /* this call reset the body */
+  int32_t reserved;
+} m3t_body_judgement;
+
 /* fills the reference's header defaults */
 static inline void m3t_region_modality_params_default(m3t_region_modality_params* p) {
   static const int s[4] = {6, 4, 2, 1};

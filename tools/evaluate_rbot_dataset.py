@@ -1,10 +1,12 @@
 """examples/evaluate_rbot_dataset.cpp over the device context (region modality, sequences without modelled
 occlusions):
 
-    python tools/evaluate_rbot_dataset.py [--batch N] RBOT_DATASET_DIR EXTERNAL_DIR [body ...]
+    python tools/evaluate_rbot_dataset.py [--batch N] [--judge-on-device] RBOT_DATASET_DIR EXTERNAL_DIR [body ...]
 
 --batch N: up to N runs share one device context (each with its own body, model, camera and optimizer); a lost body is
 reset alone (m3t_hip_reset_bodies), so the results are those of one context per run.
+--judge-on-device: the 5 cm / 5 degree judgement and the reset are the device's (m3t_hip_judge_bodies): no wait and no
+pose read per frame; "complete cycle" is then the loop's wall time per frame.
 Prints the success rate and the mean step time per (sequence, body) and overall, like
 RBOTEvaluator::VisualizeFinalResult."""
 import importlib
@@ -28,6 +30,9 @@ local_rank = int(os.environ.get("LOCAL_RANK", "0"))
 if __name__ == "__main__":
     argv = sys.argv[1:]
     batch = 1
+    judge_on_device = "--judge-on-device" in argv
+    if judge_on_device:
+        argv.remove("--judge-on-device")
     if "--batch" in argv:
         at = argv.index("--batch")
         if at + 1 >= len(argv) or not argv[at + 1].isdigit() or int(argv[at + 1]) < 1:
@@ -35,9 +40,9 @@ if __name__ == "__main__":
         batch = int(argv[at + 1])
         del argv[at:at + 2]
     if len(argv) < 2:
-        sys.exit("usage: evaluate_rbot_dataset.py [--batch N] RBOT_DATASET_DIR EXTERNAL_DIR [body ...]")
+        sys.exit("usage: evaluate_rbot_dataset.py [--batch N] [--judge-on-device] RBOT_DATASET_DIR EXTERNAL_DIR [body ...]")
     ev = pkg.evaluation
     bodies = argv[2:] or ev.RBOT_BODY_NAMES
     _, overall = ev.evaluate_rbot_dataset(lambda: pkg.open_context(local_rank), argv[0], argv[1], bodies, report=report,
-                                          shard=(rank, world), batch=batch)
+                                          shard=(rank, world), batch=batch, judge_on_device=judge_on_device)
     report("all_sequences_all_bodies", overall)

@@ -1,10 +1,12 @@
 """examples/evaluate_ycb_dataset.cpp over the device context (region + depth modality with measured occlusions,
 single-region models, tracking from the first keyframe's ground truth):
 
-    python tools/evaluate_ycb_dataset.py YCB_VIDEO_DIR EXTERNAL_DIR [sequence_id ...]
+    python tools/evaluate_ycb_dataset.py [--judge-on-device] YCB_VIDEO_DIR EXTERNAL_DIR [sequence_id ...]
 
 EXTERNAL_DIR holds poses/ground_truth/<sequence>_<body>.txt (the reference ships them as data/ycb-video_poses.zip)
-and receives models/.  Prints ADD / ADD-S AUC and the mean step time per (sequence, body) and overall."""
+and receives models/.  --judge-on-device: ADD / ADD-S are formed on the device (m3t_hip_judge_bodies), no wait and no
+pose read per frame; the execution time is then the loop's wall time per keyframe.
+Prints ADD / ADD-S AUC and the mean step time per (sequence, body) and overall."""
 import importlib
 import os
 import sys
@@ -29,9 +31,13 @@ rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE",
 local_rank = int(os.environ.get("LOCAL_RANK", "0"))
 
 if __name__ == "__main__":
+    judge_on_device = "--judge-on-device" in sys.argv
+    if judge_on_device:
+        sys.argv.remove("--judge-on-device")
     if len(sys.argv) < 3:
-        sys.exit("usage: evaluate_ycb_dataset.py YCB_VIDEO_DIR EXTERNAL_DIR [sequence_id ...]")
+        sys.exit("usage: evaluate_ycb_dataset.py [--judge-on-device] YCB_VIDEO_DIR EXTERNAL_DIR [sequence_id ...]")
     sequence_ids = [int(x) for x in sys.argv[3:]] or list(range(48, 60))  # evaluate_ycb_dataset.cpp:13
     _, overall = pkg.evaluation.evaluate_ycb_dataset(lambda: pkg.open_context(local_rank), sys.argv[1], sys.argv[2], sequence_ids,
-                                                     BODY_NAMES, report=report, shard=(rank, world))
+                                                     BODY_NAMES, report=report, shard=(rank, world),
+                                                     judge_on_device=judge_on_device)
     report("all sequences, all bodies", overall)
