@@ -204,6 +204,17 @@ BODY_JUDGEMENT_DTYPE = np.dtype([
     ("was_reset", np.int32), ("reserved", np.int32)])
 assert BODY_JUDGEMENT_DTYPE.itemsize == C.sizeof(BodyJudgement) == 32
 
+
+class StructureJudgement(C.Structure):
+    """m3t_structure_judgement: one structure's row entry of m3t_hip_judge_bodies (judge_set_structures)"""
+    _fields_ = [("add_auc", C.c_float), ("adds_auc", C.c_float), ("add_curve_zeros", C.c_int32),
+                ("adds_curve_zeros", C.c_int32)]
+
+
+STRUCTURE_JUDGEMENT_DTYPE = np.dtype([("add_auc", np.float32), ("adds_auc", np.float32),
+                                      ("add_curve_zeros", np.int32), ("adds_curve_zeros", np.int32)])
+assert STRUCTURE_JUDGEMENT_DTYPE.itemsize == C.sizeof(StructureJudgement) == 16
+
 DATA_LINE_DTYPE = np.dtype([
     ("center_f_body", np.float32, 3), ("center_u", np.float32), ("center_v", np.float32),
     ("normal_u", np.float32), ("normal_v", np.float32), ("delta_r", np.float32),
@@ -344,6 +355,9 @@ _HIP_ONLY = {
     "judge_bodies": [C.c_int, c_float_p, C.c_int, c_int_p],
     "judge_read": [C.c_int, C.c_int, C.c_int, C.c_void_p],
     "judge_clear": [C.c_int],
+    "reset_structures": [c_int_p, C.c_int, c_float_p, C.c_int, C.c_int],
+    "judge_set_structures": [C.c_int, C.c_int, c_int_p, c_int_p, c_int_p, c_float_p],
+    "judge_read_structures": [C.c_int, C.c_int, C.c_int, C.c_void_p],
 }
 
 

@@ -28,6 +28,7 @@
 #include "m3t_render.hip"
 #include "m3t_modelgen.hip"
 #include "m3t_links.hip"
+#include "m3t_structures.hip"
 #include "m3t_ingest.hip"
 
 namespace {
@@ -188,8 +189,15 @@ struct Judge {  // m3t_hip_judge_*: the evaluators' judgement of a list of bodie
   size_t stage_bytes[kStage] = {0};
   hipEvent_t stage_done[kStage] = {nullptr};
   int stage_next = 0;
+  // m3t_hip_judge_set_structures: the structures' groups of listed bodies and a second table of rows
+  int n_structures = 0;
+  DevMem d_structure_ints, d_structure_thresholds;  // [first group of each structure | first index of each group | indices]
+  size_t structure_groups = 0;
+  m3t_structure_judgement* structure_rows_host = nullptr;  // [n_rows_max][n_structures], written by the kernel in place
+  m3t_structure_judgement* structure_rows_dev = nullptr;
   ~Judge() {
     if (rows_host) (void)hipHostFree(rows_host);
+    if (structure_rows_host) (void)hipHostFree(structure_rows_host);
     for (auto& e : row_done)
       if (e) (void)hipEventDestroy(e);
     for (int i = 0; i < kStage; ++i) {
@@ -3845,6 +3853,167 @@ int m3t_hip_reset_bodies(m3t_hip_context* ctx, const int* body_ids, const float*
   }
   return M3T_OK;
 }
+// RTBEvaluator::SetBodyAndJointPoses (rtb_evaluator.cpp:809-858) + Tracker::StartModalities (tracker.cpp:430-445) for n
+// kinematic structures of the batch and for no other: the bodies' poses, the joints that follow from them, the
+// start-modality renderers, StartModality of the structures' region modalities, shared ColorHistograms included --
+// enqueued like reset_bodies (m3t_hip.h; kernels in m3t_structures.hip).
+int m3t_hip_reset_structures(m3t_hip_context* ctx, const int* optimizer_ids, int n, const float* body2world_poses, int mode,
+                             int iteration) {
+  CHECK_CTX();
+  REQUIRE(n >= 0, M3T_ERR_INVALID_ARGUMENT, "reset_structures: n must not be negative");
+  if (n == 0) return M3T_OK;
+  REQUIRE(optimizer_ids && body2world_poses, M3T_ERR_INVALID_ARGUMENT, "reset_structures: null optimizer ids or poses");
+  REQUIRE(mode == 0 || mode == 1, M3T_ERR_INVALID_ARGUMENT, "reset_structures: mode must be 0 (independent / projected) or 1 (constrained)");
+  const int n_opts = int(ctx->optimizers.size());
+  const int n_all = int(ctx->body_poses.size() / 16);
+  std::vector<char> opt_listed(size_t(n_opts), 0), listed(size_t(n_all), 0);
+  for (int i = 0; i < n; ++i) {
+    REQUIRE(optimizer_ids[i] >= 0 && optimizer_ids[i] < n_opts, M3T_ERR_INVALID_ARGUMENT, "reset_structures: bad optimizer id");
+    REQUIRE(!opt_listed[optimizer_ids[i]], M3T_ERR_INVALID_ARGUMENT, "reset_structures: an optimizer id is listed twice");
+    opt_listed[optimizer_ids[i]] = 1;
+  }
+  REQUIRE(!ctx->Distributed(), M3T_ERR_UNSUPPORTED,
+          "reset_structures: the context's structures are spread over ranks (a communicator or a reduce callback is set)");
+  // the structures' links in table order (depth first, parents before children) and what each of them takes
+  std::vector<StructureResetDev> structures;
+  std::vector<StructureLinkResetDev> entries;
+  std::vector<int> pose_body;  // body of pose k of the call
+  std::vector<int> local(ctx->links.size(), -1);
+  for (int i = 0; i < n; ++i) {
+    const Optimizer& o = ctx->optimizers[size_t(optimizer_ids[i])];
+    std::vector<int> order;
+    DfsOrder(ctx, o.link, &order);
+    const Link& root = ctx->links[size_t(o.link)];
+    REQUIRE(mode == 0 || (root.body < 0 && !root.children.empty()), M3T_ERR_INVALID_ARGUMENT,
+            "reset_structures: mode 1 (constrained) needs a root link without a body that has children");
+    structures.push_back(StructureResetDev{optimizer_ids[i], int(entries.size()), int(order.size())});
+    std::vector<int> pose_of(order.size(), -1);
+    for (size_t k = 0; k < order.size(); ++k) {
+      const Link& l = ctx->links[size_t(order[k])];
+      local[size_t(order[k])] = int(k);
+      StructureLinkResetDev e{l.body, -1, -1};
+      if (mode == 1 && k == 0) {  // :846-858: the root's link2world and joint poses stay
+        entries.push_back(e);
+        continue;
+      }
+      REQUIRE(l.body >= 0, M3T_ERR_UNSUPPORTED,
+              "reset_structures: a link without a body (the reference dereferences its body_ptr)");
+      REQUIRE(!listed[size_t(l.body)], M3T_ERR_INVALID_ARGUMENT, "reset_structures: a body belongs to two listed links");
+      REQUIRE(order.size() == 1 || !l.modalities.empty(), M3T_ERR_UNSUPPORTED,
+              "reset_structures: a body of the structure has no modality in this context (the structure's ownership "
+              "is partial: its other modalities live on another rank)");
+      listed[size_t(l.body)] = 1;
+      e.pose = pose_of[k] = int(pose_body.size());
+      pose_body.push_back(l.body);
+      if (k > 0) {
+        const int parent = local[size_t(l.parent)];
+        e.joint = (mode == 1 && parent == 0) ? -2 : pose_of[size_t(parent)];
+      }
+      entries.push_back(e);
+    }
+  }
+  std::vector<int> region_ids, renderer_ids, cameras, shared_ids;
+  for (size_t i = 0; i < ctx->region_mods.size(); ++i) {
+    const RegionMod& m = *ctx->region_mods[i];
+    if (!listed[size_t(m.body)]) continue;
+    if (m.shared_histograms >= 0 && std::find(shared_ids.begin(), shared_ids.end(), m.shared_histograms) == shared_ids.end())
+      shared_ids.push_back(m.shared_histograms);
+    region_ids.push_back(int(i));
+    cameras.push_back(m.camera);
+    if (m.depth_camera >= 0) cameras.push_back(m.depth_camera);
+    for (int renderer : {m.dev.model_occlusions ? m.depth_renderer : -1, m.dev.use_region_checking ? m.silhouette_renderer : -1})
+      if (renderer >= 0 && std::find(renderer_ids.begin(), renderer_ids.end(), renderer) == renderer_ids.end())
+        renderer_ids.push_back(renderer);
+  }
+  for (auto& m : ctx->region_mods)
+    REQUIRE(m->shared_histograms < 0 || listed[size_t(m->body)] ||
+                std::find(shared_ids.begin(), shared_ids.end(), m->shared_histograms) == shared_ids.end(),
+            M3T_ERR_UNSUPPORTED,
+            "reset_structures: shared ColorHistograms of a listed structure are also used by a modality of a structure "
+            "that is not listed (the reference defines no result for that)");
+  for (auto& m : ctx->depth_mods)
+    if (listed[size_t(m->body)]) cameras.push_back(m->camera);
+  for (int c : cameras)  // (the refusal of reset_bodies, for the cameras these structures' modalities read)
+    REQUIRE(!ctx->cameras[c]->slot_is_roi[ctx->cameras[c]->current], M3T_ERR_UNSUPPORTED,
+            "reset_structures: a frame slot the modalities read holds the trackers' rectangle only (ROI ingest); "
+            "upload the whole frame into it first (camera_upload_slot)");
+  HIPCHK(hipSetDevice(ctx->device));
+  const bool untracked_before = ctx->untracked_launches;
+  if (ctx->poses_dirty_host) ctx->roi_end_valid = false;
+  int r = Prepare(ctx, true);  // (tables and poses that were waiting for their upload anyway)
+  if (r) return r;
+  ctx->untracked_launches = untracked_before;  // tracked by a step_done event below
+  if (!ctx->tree_mode)
+    for (auto& s : structures) s.opt = -1;  // free rigid bodies only: there is no link table, the poses are all
+  // the call's arguments: [structures][links][region modality ids][renderer ids][{renderer, -1} pairs][poses]
+  const size_t n_poses = pose_body.size(), n_region = region_ids.size(), n_render = renderer_ids.size();
+  static_assert(sizeof(StructureResetDev) == 12 && sizeof(StructureLinkResetDev) == 12, "lists of ints");
+  const size_t off_entries = structures.size() * 3, off_region = off_entries + entries.size() * 3,
+               off_render = off_region + n_region, off_pairs = off_render + n_render, ints = off_pairs + 2 * n_render;
+  const size_t off_poses = (ints * 4 + 15) / 16 * 16;
+  const size_t bytes = off_poses + n_poses * 64;
+  const int stage = ctx->reset_stage_next;
+  ctx->reset_stage_next = (stage + 1) % Ctx::kResetStage;
+  if (!ctx->reset_stage_done[stage]) HIPCHK(hipEventCreateWithFlags(&ctx->reset_stage_done[stage], hipEventDisableTiming));
+  HIPCHK(hipEventSynchronize(ctx->reset_stage_done[stage]));  // the call four resets ago: normally long complete
+  if (ctx->reset_stage_bytes[stage] < bytes) {
+    if (ctx->reset_stage[stage]) HIPCHK(hipHostFree(ctx->reset_stage[stage]));
+    ctx->reset_stage[stage] = nullptr;
+    ctx->reset_stage_bytes[stage] = 0;
+    HIPCHK(hipHostMalloc(&ctx->reset_stage[stage], bytes * 2, hipHostMallocMapped));
+    ctx->reset_stage_bytes[stage] = bytes * 2;
+  }
+  int* h_ints = static_cast<int*>(ctx->reset_stage[stage]);
+  std::memcpy(h_ints, structures.data(), structures.size() * sizeof(StructureResetDev));
+  std::memcpy(h_ints + off_entries, entries.data(), entries.size() * sizeof(StructureLinkResetDev));
+  if (n_region) std::memcpy(h_ints + off_region, region_ids.data(), n_region * 4);
+  for (size_t k = 0; k < n_render; ++k) {
+    h_ints[off_render + k] = renderer_ids[k];
+    h_ints[off_pairs + 2 * k] = renderer_ids[k];
+    h_ints[off_pairs + 2 * k + 1] = -1;
+  }
+  std::memcpy(static_cast<uint8_t*>(ctx->reset_stage[stage]) + off_poses, body2world_poses, n_poses * 64);
+  void* dev = nullptr;
+  HIPCHK(hipHostGetDevicePointer(&dev, ctx->reset_stage[stage], 0));
+  const int* d_ints = static_cast<const int*>(dev);
+  hipLaunchKernelGGL(reset_structures_kernel, dim3(unsigned(structures.size())), dim3(64), 0, ctx->stream,
+                     ctx->tree_mode ? ctx->d_treeopts.as<TreeOptDev>() : (const TreeOptDev*)nullptr, ctx->d_poses.as<float>(),
+                     reinterpret_cast<const StructureResetDev*>(d_ints),
+                     reinterpret_cast<const StructureLinkResetDev*>(d_ints + off_entries),
+                     reinterpret_cast<const float*>(static_cast<const uint8_t*>(dev) + off_poses),
+                     ctx->d_region.as<RegionModDev>(), d_ints + off_region, int(n_region), iteration);
+  // the host mirrors follow: the bodies' poses; the joints stay the device's (PullLinks fetches them when asked)
+  for (size_t k = 0; k < n_poses; ++k)
+    std::memcpy(&ctx->body_poses[size_t(pose_body[k]) * 16], body2world_poses + k * 16, 64);
+  if (ctx->tree_mode) ctx->links_device_newer = true;
+  ctx->roi_end_valid = false;  // the next step's rectangles start from a snapshot of these poses
+  for (int id : region_ids) ctx->region_mods[size_t(id)]->dev.first_iteration = iteration;
+  if (n_render) {
+    int largest = 0;
+    for (int id : renderer_ids) {
+      ctx->renderers[size_t(id)]->rendered = true;
+      largest = std::max(largest, ctx->renderers[size_t(id)]->image_size);
+    }
+    if ((r = LaunchRenderers(ctx, d_ints + off_render, int(n_render), d_ints + off_pairs, int(n_render), largest))) return r;
+  }
+  if (n_region) {
+    ScopedKernelTimer timer(ctx, 1);
+    hipLaunchKernelGGL(structures_histogram_list_kernel, dim3(unsigned(n_region)), dim3(M3T_BLOCK_THREADS), ctx->lds_hist,
+                       ctx->stream, ctx->d_region.as<RegionModDev>(), d_ints + off_region, ctx->cams_active,
+                       ctx->d_poses.as<float>(), ctx->hist_counts_in_lds ? 1 : 0);
+    for (int id : shared_ids)  // InitializeHistograms of the shared objects these modalities added their samples to (tracker.cpp:441-443)
+      hipLaunchKernelGGL(shared_histogram_finish_kernel, dim3(1), dim3(M3T_BLOCK_THREADS), 0, ctx->stream,
+                         ctx->d_shared_histograms.as<SharedHistogramsDev>() + id, 1);
+  }
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(ctx->reset_stage_done[stage], ctx->stream));
+  if (ctx->async_ingest) {  // a later asynchronous upload into a slot these launches read waits for them
+    HIPCHK(hipEventRecord(ctx->step_done[ctx->step_counter % Ctx::kStepEvents], ctx->stream));
+    for (int c : cameras) ctx->cameras[c]->last_read_step[ctx->cameras[c]->current] = ctx->step_counter;
+    ++ctx->step_counter;
+  }
+  return M3T_OK;
+}
 // ---- the evaluators' judgement on the device (m3t_judge.hip) ---------------------------------------------------------
 }  // extern "C"
 namespace {
@@ -4052,6 +4221,14 @@ int m3t_hip_judge_bodies(m3t_hip_context* ctx, int judge, const float* gt_body2w
                        ctx->stream, ctx->d_region.as<RegionModDev>(), d_region_ids, d_region_body, j->d_flags.as<int>(),
                        ctx->cams_active, ctx->d_poses.as<float>(), ctx->hist_counts_in_lds ? 1 : 0);
   }
+  if (j->n_structures > 0) {  // RTBEvaluator::CalculatePoseResults' combination of the row, behind the per-body results
+    const int* d_structure_ints = j->d_structure_ints.as<int>();
+    hipLaunchKernelGGL(judge_structures_kernel, dim3(unsigned(j->n_structures + 63) / 64), dim3(64), 0, ctx->stream, d_row,
+                       d_structure_ints, d_structure_ints + j->n_structures + 1,
+                       d_structure_ints + j->n_structures + 1 + j->structure_groups + 1,
+                       j->d_structure_thresholds.as<float>(), j->n_structures,
+                       j->structure_rows_dev + size_t(row_index) * size_t(j->n_structures));
+  }
   HIPCHK(hipGetLastError());
   HIPCHK(hipEventRecord(j->stage_done[stage], ctx->stream));
   HIPCHK(hipEventRecord(j->row_done[size_t(row_index)], ctx->stream));
@@ -4079,6 +4256,73 @@ int m3t_hip_judge_read(m3t_hip_context* ctx, int judge, int first_row, int n_row
   HIPCHK(hipEventSynchronize(j->row_done[size_t(first_row + n_rows - 1)]));  // rows complete in order
   const size_t n = j->body_ids.size();
   std::memcpy(out, j->rows_host + size_t(first_row) * n, size_t(n_rows) * n * sizeof(m3t_body_judgement));
+  return M3T_OK;
+}
+// RTBEvaluator's ids_combined_bodies_ of n_structures structures: structure s holds the groups
+// [structure_first_group[s], structure_first_group[s + 1]), group g the listed bodies
+// listed_body_indices[group_first_index[g] .. group_first_index[g + 1]) (indices into the judge's list of bodies).
+// Waits for the stream and uploads: outside the frame loop, like judge_set_vertices.
+int m3t_hip_judge_set_structures(m3t_hip_context* ctx, int judge, int n_structures, const int* structure_first_group,
+                                 const int* group_first_index, const int* listed_body_indices,
+                                 const float* error_thresholds) {
+  CHECK_CTX();
+  REQUIRE(judge >= 0 && judge < int(ctx->judges.size()), M3T_ERR_INVALID_ARGUMENT, "judge_set_structures: bad judge id");
+  Judge* j = ctx->judges[size_t(judge)].get();
+  REQUIRE(n_structures >= 1 && structure_first_group && group_first_index && listed_body_indices && error_thresholds,
+          M3T_ERR_INVALID_ARGUMENT, "judge_set_structures: needs at least one structure and all four lists");
+  REQUIRE(size_t(n_structures) * size_t(j->n_rows_max) <= (size_t(1) << 23), M3T_ERR_INVALID_ARGUMENT,
+          "judge_set_structures: more than 2^23 results (n_structures x n_rows_max)");
+  REQUIRE(j->n_rows == 0, M3T_ERR_INVALID_ARGUMENT, "judge_set_structures: rows have been judged already (judge_clear first)");
+  REQUIRE(structure_first_group[0] == 0, M3T_ERR_INVALID_ARGUMENT, "judge_set_structures: the first group is group 0");
+  for (int s = 0; s < n_structures; ++s)
+    REQUIRE(structure_first_group[s + 1] > structure_first_group[s], M3T_ERR_INVALID_ARGUMENT,
+            "judge_set_structures: a structure without a group");
+  const int n_groups = structure_first_group[n_structures];
+  REQUIRE(group_first_index[0] == 0, M3T_ERR_INVALID_ARGUMENT, "judge_set_structures: the first index is index 0");
+  for (int g = 0; g < n_groups; ++g)
+    REQUIRE(group_first_index[g + 1] > group_first_index[g], M3T_ERR_INVALID_ARGUMENT,
+            "judge_set_structures: a group without a body");
+  const int n_listed = group_first_index[n_groups];
+  for (int i = 0; i < n_listed; ++i) {
+    REQUIRE(listed_body_indices[i] >= 0 && listed_body_indices[i] < int(j->body_ids.size()), M3T_ERR_INVALID_ARGUMENT,
+            "judge_set_structures: an index outside the judge's list of bodies");
+    REQUIRE(j->n_vertices[size_t(listed_body_indices[i])] > 0, M3T_ERR_INVALID_ARGUMENT,
+            "judge_set_structures: a body of a group has no evaluation vertices (judge_set_vertices first)");
+  }
+  HIPCHK(hipSetDevice(ctx->device));
+  HIPCHK(hipStreamSynchronize(ctx->stream));  // earlier calls may still read the old lists
+  std::vector<int> ints;
+  ints.insert(ints.end(), structure_first_group, structure_first_group + n_structures + 1);
+  ints.insert(ints.end(), group_first_index, group_first_index + n_groups + 1);
+  ints.insert(ints.end(), listed_body_indices, listed_body_indices + n_listed);
+  HIPCHK(j->d_structure_ints.alloc(ints.size() * 4));
+  HIPCHK(j->d_structure_thresholds.alloc(size_t(n_structures) * 4));
+  HIPCHK(hipMemcpy(j->d_structure_ints.p, ints.data(), ints.size() * 4, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(j->d_structure_thresholds.p, error_thresholds, size_t(n_structures) * 4, hipMemcpyHostToDevice));
+  if (j->structure_rows_host) HIPCHK(hipHostFree(j->structure_rows_host));
+  j->structure_rows_host = j->structure_rows_dev = nullptr;
+  j->n_structures = 0;
+  const size_t bytes = size_t(n_structures) * size_t(j->n_rows_max) * sizeof(m3t_structure_judgement);
+  HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&j->structure_rows_host), bytes, hipHostMallocMapped));
+  std::memset(j->structure_rows_host, 0, bytes);
+  HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&j->structure_rows_dev), j->structure_rows_host, 0));
+  j->n_structures = n_structures;
+  j->structure_groups = size_t(n_groups);
+  return M3T_OK;
+}
+int m3t_hip_judge_read_structures(m3t_hip_context* ctx, int judge, int first_row, int n_rows, m3t_structure_judgement* out) {
+  CHECK_CTX();
+  REQUIRE(judge >= 0 && judge < int(ctx->judges.size()), M3T_ERR_INVALID_ARGUMENT, "judge_read_structures: bad judge id");
+  Judge* j = ctx->judges[size_t(judge)].get();
+  REQUIRE(j->n_structures > 0, M3T_ERR_INVALID_ARGUMENT, "judge_read_structures: judge_set_structures first");
+  REQUIRE(first_row >= 0 && n_rows >= 0 && first_row <= j->n_rows && n_rows <= j->n_rows - first_row,
+          M3T_ERR_INVALID_ARGUMENT, "judge_read_structures: rows that have not been judged");
+  if (n_rows == 0) return M3T_OK;
+  REQUIRE(out, M3T_ERR_INVALID_ARGUMENT, "judge_read_structures: null output");
+  HIPCHK(hipSetDevice(ctx->device));
+  HIPCHK(hipEventSynchronize(j->row_done[size_t(first_row + n_rows - 1)]));  // rows complete in order
+  const size_t n = size_t(j->n_structures);
+  std::memcpy(out, j->structure_rows_host + size_t(first_row) * n, size_t(n_rows) * n * sizeof(m3t_structure_judgement));
   return M3T_OK;
 }
 int m3t_hip_judge_clear(m3t_hip_context* ctx, int judge) {

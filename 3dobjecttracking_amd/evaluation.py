@@ -291,6 +291,213 @@ def evaluate_ycb_sequence(tracker, bodies, evaluations, gt_body2world_poses, key
 
 
 # ---------------------------------------------------------------------------------------------------------
+# RTB (M3T/examples/rtb_evaluator.cpp): kinematic structures
+# ---------------------------------------------------------------------------------------------------------
+RTB_N_CURVE_VALUES = 100  # rtb_evaluator.h kNCurveValues
+
+
+def rtb_thresholds():
+    """rtb_evaluator.cpp:20-24"""
+    step = F(1.0) / F(RTB_N_CURVE_VALUES)
+    return np.asarray([step * (F(0.5) + F(i)) for i in range(RTB_N_CURVE_VALUES)], F)
+
+
+def rtb_pose_result(errors_per_body, groups, error_threshold):
+    """RTBEvaluator::CalculatePoseResults (rtb_evaluator.cpp:935-988) from the per-body (ADD, ADD-S) errors, in f32 op
+    by op: per group of combined bodies the members' errors summed in listed order and divided by their number, per
+    structure 1 - min(err / threshold, 1) summed over the groups and divided by their number; the curves are 0 up to
+    the first threshold above the auc.  `errors_per_body[i]` = (add, adds) of body i, `groups` lists of such i.
+    The host twin of m3t_hip_judge_set_structures."""
+    thresholds = rtb_thresholds()
+    out = {}
+    for key, which in (("add", 0), ("adds", 1)):
+        auc = F(0.0)
+        for group in groups:
+            err = F(0.0)
+            for i in group:
+                err = F(err + F(errors_per_body[i][which]))
+            err = F(err / F(len(group)))
+            auc = F(auc + F(F(1.0) - min(F(err / F(error_threshold)), F(1.0))))
+        auc = F(auc / F(len(groups)))
+        curve = np.ones(RTB_N_CURVE_VALUES, F)
+        zeros = 0
+        while zeros < RTB_N_CURVE_VALUES and not auc < thresholds[zeros]:
+            curve[zeros] = 0.0
+            zeros += 1
+        out[key + "_auc"] = float(auc)
+        out[key + "_curve"] = curve
+        out[key + "_curve_zeros"] = zeros
+    return out
+
+
+class RTBStructure:
+    """What evaluate_rtb_sequences needs of one kinematic structure: its optimizer, its links in depth-first order as
+    (Link, Body or None, index of the parent link in this list or -1), the evaluation of every body (an object with
+    .vertices and .errors(pose, gt) such as YCBBodyEvaluation) in the order of the links that have one, RTB's combined
+    bodies as lists of indices into that order, the error threshold and the evaluation mode (0 independent /
+    projected, 1 constrained: body-less root)."""
+
+    def __init__(self, optimizer, links, evaluations, groups, error_threshold, mode=0):
+        self.optimizer, self.links, self.evaluations, self.groups = optimizer, list(links), list(evaluations), groups
+        self.error_threshold, self.mode = float(error_threshold), int(mode)
+        self.bodies = [body for _, body, _ in self.links if body is not None]
+        assert len(self.bodies) == len(self.evaluations)
+
+
+def _mul_pose_f32(a, b):
+    """Transform3fA * Transform3fA in f32, one rounding per operation, sums left to right"""
+    r = np.zeros((4, 4), F)
+    r[3, 3] = 1.0
+    for c in range(3):
+        for k in range(3):
+            r[k, c] = F(F(F(a[k, 0] * b[0, c]) + F(a[k, 1] * b[1, c])) + F(a[k, 2] * b[2, c]))
+    for k in range(3):
+        r[k, 3] = F(F(F(F(a[k, 0] * b[0, 3]) + F(a[k, 1] * b[1, 3])) + F(a[k, 2] * b[2, 3])) + a[k, 3])
+    return r
+
+
+def _inverse_pose_f32(a):
+    """Transform3fA::inverse() (Affine): the cofactor inverse of the linear part, t' = -(L^-1 t)"""
+    m = a[:3, :3]
+
+    def cof(i, j):
+        i1, i2, j1, j2 = (i + 1) % 3, (i + 2) % 3, (j + 1) % 3, (j + 2) % 3
+        return F(F(m[i1, j1] * m[i2, j2]) - F(m[i1, j2] * m[i2, j1]))
+
+    c00, c10, c20 = cof(0, 0), cof(1, 0), cof(2, 0)
+    det = F(F(F(c00 * m[0, 0]) + F(c10 * m[1, 0])) + F(c20 * m[2, 0]))
+    invdet = F(F(1.0) / det)
+    r = np.zeros((4, 4), F)
+    r[3, 3] = 1.0
+    for rr in range(3):
+        for cc in range(3):
+            r[rr, cc] = F(cof(cc, rr) * invdet)
+    for k in range(3):
+        r[k, 3] = -F(F(F(r[k, 0] * a[0, 3]) + F(r[k, 1] * a[1, 3])) + F(r[k, 2] * a[2, 3]))
+    return r
+
+
+def set_body_and_joint_poses(structure, poses):
+    """RTBEvaluator::SetBodyAndJointPoses (rtb_evaluator.cpp:809-858) on the host objects of one structure (any
+    library): what Tracker.ResetStructures does on the device, minus the restart of the modalities"""
+    pose_of, k = {}, 0
+    for index, (link, body, parent) in enumerate(structure.links):
+        if body is None:
+            assert structure.mode == 1 and index == 0, "only the root of mode 1 may have no body"
+            continue
+        pose = np.asarray(poses[k], F)
+        pose_of[index] = pose
+        k += 1
+        body.set_body2world_pose(pose)
+        if parent < 0:
+            continue
+        if structure.mode == 1 and parent == 0:
+            link.set_joint2parent_pose(pose)
+        else:
+            link.set_joint2parent_pose(_mul_pose_f32(_mul_pose_f32(_inverse_pose_f32(pose_of[parent]), pose),
+                                                     _inverse_pose_f32(np.asarray(link.body2joint_pose(), F))))
+
+
+def evaluate_rtb_sequences(tracker, structures, gt_poses_per_structure, load_images, judge_on_device=False):
+    """The loop of RTBEvaluator::EvaluateRunConfiguration (rtb_evaluator.cpp:465-495) for S kinematic structures in ONE
+    context, each with a list of sequences of its own: gt_poses_per_structure[s][q][k][b] is the ground-truth pose of
+    body b of structure s in image k of its sequence q (bodies in RTBStructure.bodies order).  A structure starts a
+    sequence on image 0 at its ground truth (SetBodyAndJointPoses + StartModalities, :466-467); cycle i tracks image
+    i + 1 and is judged against its ground truth (CalculatePoseResults).  The sequences may have different lengths: a
+    structure whose sequence has ended is put on the first pose of its next one with Tracker.ResetStructures while the
+    others keep tracking, so each structure's results are those of a tracker of its own.  The step's iteration number
+    is the batch's cycle counter and a structure's first_iteration the cycle it started on: their difference -- all the
+    modalities read -- is the sequence's own cycle index.  `load_images(s, q, k)` makes image k of sequence q current
+    in the cameras of structure s.
+    A library without reset_structures (the oracle) can only restart all structures of the context together: one
+    structure, or sequences of equal length.
+    judge_on_device (HIP library): ADD / ADD-S and their combination are formed on the device (Judge.set_structures);
+    nothing is read before the last cycle.
+    Returns results[s][q] = list of per-cycle dicts (frame_index, add_auc, adds_auc, add_curve, adds_curve)."""
+    n = len(structures)
+    device_reset = "reset_structures" in tracker.api._fn
+    results = [[[] for _ in sequences] for sequences in gt_poses_per_structure]
+    state = [[0, 0] for _ in range(n)]  # sequence, cycle inside it
+
+    def start(which, iteration):
+        for s in which:
+            load_images(s, state[s][0], 0)
+        if device_reset:
+            for mode in sorted({structures[s].mode for s in which}):
+                group = [s for s in which if structures[s].mode == mode]
+                poses = [p for s in group for p in gt_poses_per_structure[s][state[s][0]][0]]
+                if not tracker.ResetStructures([structures[s].optimizer for s in group], poses, mode, iteration):
+                    raise RuntimeError("ResetStructures failed")
+            return
+        if len(which) != n:
+            raise RuntimeError("this library restarts all structures of a context together (no reset_structures)")
+        for s in which:
+            set_body_and_joint_poses(structures[s], gt_poses_per_structure[s][state[s][0]][0])
+        if not tracker.StartModalities(iteration):
+            raise RuntimeError("StartModalities failed")
+
+    active = [s for s in range(n) if len(gt_poses_per_structure[s]) > 0]
+    start(active, 0)
+    judge, pending, first_body = None, [], np.cumsum([0] + [len(st.bodies) for st in structures])
+    if judge_on_device:
+        total = sum(len(seq) - 1 for sequences in gt_poses_per_structure for seq in sequences)
+        judge = tracker.CreateJudge([b for st in structures for b in st.bodies], max(1, total))
+        for s, st in enumerate(structures):
+            for b, evaluation in enumerate(st.evaluations):
+                judge.set_vertices(int(first_body[s]) + b, evaluation.vertices)
+        judge.set_structures([[[int(first_body[s]) + b for b in group] for group in st.groups]
+                              for s, st in enumerate(structures)], [st.error_threshold for st in structures])
+        last_gt = [list(gt_poses_per_structure[s][0][0]) if gt_poses_per_structure[s] else [np.eye(4, dtype=F)] * len(st.bodies)
+                   for s, st in enumerate(structures)]
+    cycle = 0
+    while active:
+        for s in active:
+            load_images(s, state[s][0], state[s][1] + 1)
+        if not tracker.ExecuteTrackingStep(cycle):
+            raise RuntimeError("tracking step %d failed" % cycle)
+        if judge_on_device:
+            for s in active:
+                last_gt[s] = list(gt_poses_per_structure[s][state[s][0]][state[s][1] + 1])
+            row = judge.judge([p for gt in last_gt for p in gt], -1)
+            pending += [(row, s, state[s][0], state[s][1]) for s in active]
+        else:
+            if not tracker.Sync():
+                raise RuntimeError("tracking step %d failed" % cycle)
+            for s in active:
+                st, (q, i) = structures[s], state[s]
+                gt = gt_poses_per_structure[s][q][i + 1]
+                errors = [ev.errors(body.body2world_pose(), g) for ev, body, g in zip(st.evaluations, st.bodies, gt)]
+                r = rtb_pose_result(errors, st.groups, st.error_threshold)
+                r.update(frame_index=i)
+                results[s][q].append(r)
+        ended = []
+        for s in list(active):
+            state[s][1] += 1
+            if state[s][1] + 1 < len(gt_poses_per_structure[s][state[s][0]]):
+                continue
+            state[s] = [state[s][0] + 1, 0]
+            if state[s][0] < len(gt_poses_per_structure[s]):
+                ended.append(s)
+            else:
+                active.remove(s)
+        cycle += 1
+        if ended:
+            start(ended, cycle)
+    if judge_on_device and pending:
+        rows = judge.read_structures(0, pending[-1][0] + 1)
+        for row, s, q, i in pending:
+            r = rows[row, s]
+            out = dict(frame_index=i)
+            for key in ("add", "adds"):
+                zeros = int(r[key + "_curve_zeros"])
+                curve = np.ones(RTB_N_CURVE_VALUES, F)
+                curve[:zeros] = 0.0
+                out.update({key + "_auc": float(r[key + "_auc"]), key + "_curve": curve, key + "_curve_zeros": zeros})
+            results[s][q].append(out)
+    return results
+
+
+# ---------------------------------------------------------------------------------------------------------
 # RBOT dataset driver (examples/evaluate_rbot_dataset.cpp + rbot_evaluator.cpp)
 # ---------------------------------------------------------------------------------------------------------
 RBOT_INTRINSICS = (650.048, 647.183, 324.328 - 0.5, 257.323 - 0.5, 640, 512)  # rbot_evaluator.h:40-41

@@ -83,6 +83,19 @@ class Tracker:
             raise M3TError(-3, "%sreset_bodies: this entry point exists in the HIP library only" % self.api.prefix)
         return self._step("reset_bodies", iptr(ids), fptr(flat) if flat is not None else None, len(ids), iteration)
 
+    def ResetStructures(self, optimizers, poses, mode=0, iteration=0):
+        """RTBEvaluator::SetBodyAndJointPoses (rtb_evaluator.cpp:809-858) + StartModalities(iteration) for the
+        kinematic structures `optimizers` alone, in one call (HIP library only).  `poses`: one body2world pose per link
+        that has a body, concatenated over the optimizers in each one's depth-first link order; mode 0: independent /
+        projected, 1: constrained (body-less root, the poses start at its children).  Every other structure keeps its
+        state bit for bit (m3t_hip_reset_structures)."""
+        ids = np.asarray([o.id for o in optimizers], np.int32)
+        flat = np.ascontiguousarray(np.concatenate([pose_arg(p) for p in poses]) if len(poses) else
+                                    np.zeros(0, np.float32), np.float32)
+        if "reset_structures" not in self.api._fn:
+            raise M3TError(-3, "%sreset_structures: this entry point exists in the HIP library only" % self.api.prefix)
+        return self._step("reset_structures", iptr(ids), len(ids), fptr(flat), int(mode), int(iteration))
+
     def CreateJudge(self, bodies, n_rows_max):
         """the evaluators' judgement of `bodies` on the device (HIP library only): see Judge"""
         return Judge(self.api, bodies, n_rows_max)
@@ -164,6 +177,30 @@ class Judge:
 
     def clear(self):
         self.api.call("judge_clear", self.id)
+
+    def set_structures(self, structures, error_thresholds):
+        """RTBEvaluator's ids_combined_bodies_ per structure: `structures` is a list (one entry per structure) of lists
+        of groups, a group being a list of listed bodies (Body objects or indices into the judge's list);
+        `error_thresholds`: one per structure.  Every later `judge` also writes a row of structure judgements."""
+        ids = [b.id for b in self.bodies]
+        first_group, first_index, listed = [0], [0], []
+        for groups in structures:
+            for group in groups:
+                listed += [int(b) if isinstance(b, (int, np.integer)) else ids.index(b.id) for b in group]
+                first_index.append(len(listed))
+            first_group.append(len(first_index) - 1)
+        thresholds = np.ascontiguousarray(error_thresholds, np.float32).reshape(-1)
+        assert len(thresholds) == len(structures)
+        self.n_structures = len(structures)
+        self.api.call("judge_set_structures", self.id, self.n_structures, iptr(np.asarray(first_group, np.int32)),
+                      iptr(np.asarray(first_index, np.int32)), iptr(np.asarray(listed + [0], np.int32)), fptr(thresholds))
+
+    def read_structures(self, first_row, n_rows):
+        """structure rows [first_row, first_row + n_rows) as a structured array [n_rows][n_structures]
+        (STRUCTURE_JUDGEMENT_DTYPE); waits for the last of them only"""
+        out = np.zeros((n_rows, self.n_structures), _capi.STRUCTURE_JUDGEMENT_DTYPE)
+        self.api.call("judge_read_structures", self.id, int(first_row), int(n_rows), out.ctypes.data_as(C.c_void_p))
+        return out
 
 
 class Body:

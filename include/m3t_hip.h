@@ -309,6 +309,44 @@ int m3t_hip_start_modalities(m3t_hip_context*, int iteration);                  
  * A body without modalities only gets its pose. */
 int m3t_hip_reset_bodies(m3t_hip_context*, const int* body_ids, const float* body2world_poses /* n x 16, or NULL */,
                          int n, int iteration);
+/* RTBEvaluator::SetBodyAndJointPoses (examples/rtb_evaluator.cpp:809-858) followed by Tracker::StartModalities
+ * (tracker.cpp:430-445) for n kinematic structures of the batch -- the optimizers listed -- and for no other: what an
+ * evaluator of independent structure sequences does when one of them starts its (next) sequence.
+ *   - body2world_poses: one pose (16 floats, column-major) per link that has a body, concatenated over the listed
+ *     optimizers in each optimizer's depth-first link order: the root, then for every child in the order the children
+ *     were created the child followed by its own subtree (the order of the device's link table).  A body-less root of
+ *     mode 1 takes no pose.
+ *   - mode 0 (EvaluationMode INDEPENDENT / PROJECTED, :823-844): every link's body gets its pose, and a link with a parent
+ *     joint2parent = (parent body2world^-1 * body2world) * body2joint^-1, in f32, evaluated left to right with the
+ *     library's restatement of Eigen's Transform3fA product and inverse.  body2joint is the value ON THE DEVICE: for a
+ *     link with fixed_body2joint_pose == 0 tracking has moved it.  link2world of the link becomes the pose.
+ *   - mode 1 (CONSTRAINED, :846-858): the root has no body; its link2world and joint poses stay.  Every child of the
+ *     root gets its pose and joint2parent = that pose, bit for bit; below those children mode 0's rule applies.
+ *   - the restart is StartModalities(iteration) restricted to the listed structures: the start-modality renderers their
+ *     region modalities read are run; first_iteration = iteration and StartModality(iteration, 0) for those modalities.
+ *     Shared ColorHistograms the listed modalities use are cleared, filled by those modalities and initialised
+ *     (tracker.cpp:435-443), as start_modalities does for the whole context.
+ * Every other structure stays as it was, bit for bit: body poses, joint poses, histograms, first_iteration, line and
+ * point state and the g/H of the last step.  No device state that follows a joint pose outlives a step (the tree
+ * kernels rebuild adjoints and Jacobians from the link table in every launch), so the link table and the poses are all
+ * the call writes.  It is enqueued on the context's stream like reset_bodies: it reads nothing back, does not wait for
+ * the stream and uploads no table (tables and host-set poses already waiting for their upload go up as in any other
+ * call); the arguments cross through the same ring of mapped host blocks.  The host mirrors follow as after
+ * reset_bodies: the joints stay device-authoritative (link_get_joint_poses fetches them), the body-pose mirror takes the
+ * new poses, the next step's ROI rectangles start from a fresh snapshot, the compact kernel's overflow latch is left
+ * alone.  A single-link structure (optimizer_create_rigid or a lone link) is accepted with mode 0 and behaves exactly as
+ * reset_bodies does on its body.
+ * Arguments are checked before anything changes; a failed call leaves the context as it was:
+ *   M3T_ERR_INVALID_ARGUMENT  n < 0, a bad or repeated optimizer id, an unknown mode, mode 1 on a root that has a body or
+ *                             no children;  n == 0: M3T_OK, nothing happens
+ *   M3T_ERR_UNSUPPORTED       a link without a body other than the root of mode 1 (the reference dereferences its
+ *                             body_ptr); shared ColorHistograms that a modality of a structure NOT listed uses as well
+ *                             (the reference defines no result); ROI ingest: a camera the listed bodies' modalities read
+ *                             whose current slot holds a rectangle only; structures spread over ranks: a communicator
+ *                             or a reduce callback is set, or a body of a listed structure of several links has no
+ *                             modality in this context. */
+int m3t_hip_reset_structures(m3t_hip_context*, const int* optimizer_ids, int n, const float* body2world_poses, int mode,
+                             int iteration);
 /* The evaluators' judgement on the device.  A judge holds a list of bodies, their evaluation vertices (optional) and a
  * table of n_rows_max result rows of n_bodies m3t_body_judgement each.
  * judge_bodies judges every listed body against its ground-truth pose (n_bodies x 16, column-major) into the next row:
@@ -338,7 +376,23 @@ int m3t_hip_reset_bodies(m3t_hip_context*, const int* body_ids, const float* bod
  * After a resetting call the host's pose mirror does not vouch for these bodies (as after reset_bodies with poses).
  * judge_read waits for the event of the last requested row only and copies rows [first_row, first_row + n_rows) to
  * out[n_rows][n_bodies]; judge_clear starts the rows at 0 again.  judge_set_vertices (1 <= n <= 1 << 18 vertices of
- * body_ids[index], xyz) and judge_create wait for the stream and upload; call them outside the frame loop. */
+ * body_ids[index], xyz) and judge_create wait for the stream and upload; call them outside the frame loop.
+ * Structures (RTBEvaluator::CalculatePoseResults, examples/rtb_evaluator.cpp:930-989).  judge_set_structures gives the
+ * judge RTB's ids_combined_bodies_ for n_structures structures: structure s holds the groups
+ * [structure_first_group[s], structure_first_group[s + 1]), group g the bodies
+ * listed_body_indices[group_first_index[g] .. group_first_index[g + 1]) -- indices into the judge's list of bodies --
+ * and error_thresholds[s] is its error_threshold_.  From then on every judge_bodies call also writes one row of
+ * n_structures m3t_structure_judgement behind the per-body results, in RTB's f32 arithmetic op by op: per group the
+ * members' add_error / adds_error (exactly what the row holds) summed left to right in listed order and divided by the
+ * member count; per structure 1.0f - fminf(err / threshold, 1.0f) summed over its groups and divided by the group
+ * count; *_curve_zeros = the first i in [0, 100) with auc < (1.0f / 100.0f) * (0.5f + float(i)) (:20-24), 100 if there
+ * is none: the number of leading curve entries the reference sets to 0.  The reference sums the per-body vertex errors
+ * in f32; the judge keeps its f64 fixed-order sums, as for YCB.  The per-body rows and their bits do not change, and
+ * reset_iteration >= 0 keeps its meaning and its refusals (RTB never resets on loss).  judge_set_structures waits for
+ * the stream and uploads (outside the frame loop); M3T_ERR_INVALID_ARGUMENT: a bad judge, lists that are not ascending
+ * from 0, an empty structure or group, an index outside the judge's list, a body of a group without evaluation
+ * vertices, rows already judged (judge_clear first).  judge_read_structures is judge_read for these rows:
+ * out[n_rows][n_structures]. */
 int m3t_hip_judge_create(m3t_hip_context*, const int* body_ids, int n_bodies, int n_rows_max, int* judge);
 int m3t_hip_judge_set_thresholds(m3t_hip_context*, int judge, float translation_error_threshold,
                                  float rotation_error_threshold);
@@ -346,6 +400,12 @@ int m3t_hip_judge_set_vertices(m3t_hip_context*, int judge, int index, const flo
 int m3t_hip_judge_bodies(m3t_hip_context*, int judge, const float* gt_body2world_poses, int reset_iteration, int* row);
 int m3t_hip_judge_read(m3t_hip_context*, int judge, int first_row, int n_rows, m3t_body_judgement* out);
 int m3t_hip_judge_clear(m3t_hip_context*, int judge);
+int m3t_hip_judge_set_structures(m3t_hip_context*, int judge, int n_structures,
+                                 const int* structure_first_group /* n_structures + 1 */,
+                                 const int* group_first_index /* n_groups + 1 */, const int* listed_body_indices,
+                                 const float* error_thresholds /* n_structures */);
+int m3t_hip_judge_read_structures(m3t_hip_context*, int judge, int first_row, int n_rows,
+                                  m3t_structure_judgement* out /* [n_rows][n_structures] */);
 int m3t_hip_calculate_correspondences(m3t_hip_context*, int iteration, int corr_iteration); /* :447 */
 int m3t_hip_calculate_gradient_and_hessian(m3t_hip_context*, int iteration, int corr_iteration,
                                            int opt_iteration);                    /* :471 */

@@ -458,6 +458,16 @@ class Tracker {
     return c_->Step(m3t_hip_reset_bodies(c_->get(), body_ids.data(), poses.empty() ? nullptr : poses[0].data(),
                                          int(body_ids.size()), iteration));
   }
+  // RTBEvaluator::SetBodyAndJointPoses (rtb_evaluator.cpp:809-858) + StartModalities(iteration) for the listed kinematic
+  // structures alone (m3t_hip_reset_structures): one pose per link that has a body, concatenated over the optimizers in
+  // each one's depth-first link order; mode 0: independent / projected, 1: constrained (body-less root)
+  bool ResetStructures(const std::vector<const Optimizer*>& optimizers, const std::vector<Pose>& poses, int mode = 0,
+                       int iteration = 0) {
+    std::vector<int> optimizer_ids;
+    for (const Optimizer* optimizer : optimizers) optimizer_ids.push_back(optimizer->id());
+    return c_->Step(m3t_hip_reset_structures(c_->get(), optimizer_ids.data(), int(optimizer_ids.size()),
+                                             poses.empty() ? nullptr : poses[0].data(), mode, iteration));
+  }
 
   // The evaluators' judgement on the device (m3t_hip_judge_*): CalculatePoseResults of RBOTEvaluator / YCBEvaluator for
   // a list of bodies, ResetBody of the bodies the device finds lost (reset_iteration >= 0).  Judge() is enqueued behind
@@ -488,11 +498,33 @@ class Tracker {
       return out;
     }
     void Clear() { c_->Check(m3t_hip_judge_clear(c_->get(), id_), "Judge"); }
+    // RTBEvaluator::CalculatePoseResults (rtb_evaluator.cpp:930-989): structures[s] = the groups of combined bodies of
+    // structure s, a group = indices into the judge's list of bodies; every later JudgeBodies also fills a structure row
+    void SetStructures(const std::vector<std::vector<std::vector<int>>>& structures, const std::vector<float>& error_thresholds) {
+      std::vector<int> first_group{0}, first_index{0}, listed;
+      for (const auto& groups : structures) {
+        for (const auto& group : groups) {
+          listed.insert(listed.end(), group.begin(), group.end());
+          first_index.push_back(int(listed.size()));
+        }
+        first_group.push_back(int(first_index.size()) - 1);
+      }
+      listed.push_back(0);  // (data() of an empty list is no pointer)
+      c_->Check(error_thresholds.size() == structures.size() ? m3t_hip_judge_set_structures(
+                    c_->get(), id_, int(structures.size()), first_group.data(), first_index.data(), listed.data(),
+                    error_thresholds.data()) : M3T_ERR_INVALID_ARGUMENT, "Judge");
+      n_structures_ = structures.size();
+    }
+    std::vector<m3t_structure_judgement> ReadStructures(int first_row, int n_rows) const {  // [n_rows][n_structures]
+      std::vector<m3t_structure_judgement> out(size_t(n_rows > 0 ? n_rows : 0) * n_structures_);
+      c_->Check(m3t_hip_judge_read_structures(c_->get(), id_, first_row, n_rows, out.data()), "Judge");
+      return out;
+    }
     size_t n_bodies() const { return n_; }
 
    private:
     ContextPtr c_;
-    size_t n_;
+    size_t n_, n_structures_ = 0;
     int id_ = -1;
   };
   Judge CreateJudge(const std::vector<const Body*>& bodies, int n_rows_max) { return Judge(c_, bodies, n_rows_max); }

@@ -200,6 +200,14 @@ typedef struct m3t_body_judgement {
   int32_t reserved;
 } m3t_body_judgement;
 
+/* One structure's judgement by m3t_hip_judge_bodies once m3t_hip_judge_set_structures has been called:
+ * RTBEvaluator::CalculatePoseResults (examples/rtb_evaluator.cpp:930-989).  *_curve_zeros: how many leading entries of
+ * the reference's add_curve / adds_curve are 0 (the others are 1).  16 bytes. */
+typedef struct m3t_structure_judgement {
+  float add_auc, adds_auc;
+  int32_t add_curve_zeros, adds_curve_zeros;
+} m3t_structure_judgement;
+
 /* fills the reference's header defaults */
 static inline void m3t_region_modality_params_default(m3t_region_modality_params* p) {
   static const int s[4] = {6, 4, 2, 1};
