@@ -4617,7 +4617,7 @@ int m3t_hip_execute_tracking_step(m3t_hip_context* ctx, int iteration) {
     const bool pair = !roi_frames && !ctx->region_mods.empty() && !ctx->depth_mods.empty() && !std::getenv("M3T_HIP_NO_PAIR");
     // Region-only batches whose first Newton step after a search reads no distribution row (n_global_iterations >= 1)
     // and whose searches have no occlusion vote to defer: the split kernel with the moments-first exchange
-    // (m3t_kernels.hip, split_exchange_publish_moments).  Every object of the launch must qualify; all others keep
+    // (m3t_kernels.hip, region_distribution_rows).  Every object of the launch must qualify; all others keep
     // tracking_step_split_kernel.  M3T_HIP_NO_MOMENTS_FIRST: developer override.
     bool moments_first = !roi_frames && !pair && ctx->depth_mods.empty() && !ctx->region_mods.empty() &&
                          ctx->n_update_iterations >= 1 && !std::getenv("M3T_HIP_NO_MOMENTS_FIRST");

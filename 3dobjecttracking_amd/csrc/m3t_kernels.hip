@@ -29,6 +29,7 @@
 #include <limits.h>
 
 #include "m3t_device.h"
+#include "m3t_dist_rows.h"
 #include "m3t_log.h"
 #include "m3t_renderer_read.h"
 #include "m3t_roi.h"
@@ -845,12 +846,19 @@ constexpr int kExchangeFieldBits = 5;
 
 // RENDER = false: a launch shape that never runs with renderer-fed branches (the split kernel: m3t_hip_api.hip takes
 // the per-search launches of tracking_step_kernel as soon as a modality reads a rendering) leaves their code out
-template <bool HIST_LDS, int BMAX = 8, bool RENDER = true, bool LEAN = false>
+// ROWS = true (tracking_step_split_moments_kernel): the function leaves behind phase B's barrier and says in *walked
+// which lines were walked; distributions and moments follow in region_distribution_rows
+struct RegionWalked {
+  int n_lines_b;   // the view's lines below the part's end
+  int valid_mask;  // bit of LS_VALID that phase B tested
+};
+template <bool HIST_LDS, int BMAX = 8, bool RENDER = true, bool LEAN = false, bool ROWS = false>
 __device__ __forceinline__ int region_correspondences(CRegion& m, CCam& cam, CCam* dcam, const Affine& b2c,
                                                        const Affine& b2dc, int iteration, int corr_iteration,
                                                        const Lds& s, int line_lo = 0, int line_hi = 1 << 30,
                                                        bool* vote_deferred = nullptr, int prev_view = -1,
-                                                       const SplitExchange* early = nullptr) {
+                                                       const SplitExchange* early = nullptr,
+                                                       RegionWalked* walked = nullptr) {
   // early: the thread that normalises a distribution value (phase C2) also sends it to the object's other workgroups
   // (the granule split_exchange_publish would write after the phase: same slot, same tag, same value), unless the
   // occlusion vote is deferred -- then the rows travel with the flags after the phase
@@ -1068,6 +1076,13 @@ __device__ __forceinline__ int region_correspondences(CRegion& m, CCam& cam, CCa
   }
   __syncthreads();
   PHASE_MARK(2);
+  if constexpr (ROWS) {
+    // (the final flag, bit 0 of LS_VALID, stands since phase A: without an occlusion pass -- the host vouches -- a valid
+    // line carries bits 0 and 1, an invalid one neither, and valid_mask is 2)
+    walked->n_lines_b = n_lines_b;
+    walked->valid_mask = valid_mask;
+    return view;
+  }
 
   // ---- phase C1: raw distribution products (aliases the chain buffer) ----
   const int dl = m.distribution_length, fl = m.function_length;
@@ -1589,28 +1604,117 @@ __device__ __forceinline__ bool split_exchange_collect(const SplitExchange& x, i
 // Moments-first exchange (tracking_step_split_moments_kernel: Region-only objects, no deferred occlusion vote,
 // n_global_iterations >= 1).  The first Newton step after a search takes the global branch of region_products, which
 // reads a line's mean and variance but not its distribution; so only those two values per line sit on the critical
-// path: the part that owns a line takes its moments (the same code on the same bits a receiver would run) and sends
-// them as the fields distribution_length and distribution_length + 1 of its slot, and the distribution rows
-// -- sent by phase C2 as before -- are collected by the waves that would otherwise wait at the barrier behind the first
-// Newton step's chain and solve (wave 0).  That barrier is the join: no part publishes anything of round c + 1 before
-// it holds every granule of round c, which is what the alternating slots need (see above).
+// path: the part that owns a line takes its moments (the same expressions on the same bits a receiver would run) and
+// sends them as the fields distribution_length and distribution_length + 1 of its slot (region_distribution_rows below),
+// and the distribution rows -- sent by the same pass -- are collected by the waves that would otherwise wait at the
+// barrier behind the first Newton step's chain and solve (wave 0).  That barrier is the join: no part publishes anything
+// of round c + 1 before it holds every granule of round c, which is what the alternating slots need (see above).
 // ---------------------------------------------------------------------------
-// the moments of the own lines [lo, hi), and their granules; no barrier (every thread sends what it wrote itself).
-// Lines beyond the view's lines and invalid lines send what their row holds: the receivers wait for every granule.
-__device__ __forceinline__ void split_exchange_publish_moments(const SplitExchange& x, int round, CRegion& m, const Lds& s,
-                                                               int lo, int hi) {
-  region_moments(m, s, lo, hi, true);
-  const int nl = s.nl, f_mean = m.distribution_length;
-  auto* mine = x.granules + (((size_t)(round & 1) * x.n_parts + x.part) << (kExchangeFieldBits + x.lshift));
-  const unsigned long long tag_bits = static_cast<unsigned long long>(x.seq * 64u + (uint32_t)round + 1u) << 32;
-  for (int line = threadIdx.x; line < nl; line += blockDim.x) {  // (the thread -> line map of region_moments_lines)
-    if (line < lo || line >= hi) continue;
-    const float mean = s.state[LS_MEAN * nl + line], var = s.state[LS_VAR * nl + line];
-    __hip_atomic_store(mine + ((f_mean << x.lshift) | (line - lo)), tag_bits | (unsigned)__float_as_int(mean),
-                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(mine + (((f_mean + 1) << x.lshift) | (line - lo)), tag_bits | (unsigned)__float_as_int(var),
-                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+// The row pass (tracking_step_split_moments_kernel): phases C1 and C2 of region_correspondences and the owner's moments
+// (region_moments_lines, two granules per line) in one pass without a workgroup barrier.  A line's
+// distribution values sit in one 16-lane row of one wave (m3t_dist_rows.h), lane d holding value d:
+//   raw product   as phase C1 forms it (same reads, same order of the products);
+//   area          (((0 + v0) + v1) + ...): a chain of row_shr:1 DPP additions -- every lane adds its own term to what its
+//                 left neighbour holds, so after step k the lanes 0 .. k hold the reference's prefixes 0 .. k and lane
+//                 dl - 1 ends with the sum; one row-local ds_bpermute hands it to the row;
+//   value         raw / area, stored to its state row and sent (the granule phase C2 sends);
+//   mean, var     two more such chains over (float)d * value and ((float)d - mean)^2 * value (region_moments_lines'
+//                 expressions, nothing contracted); lane dl - 1 stores them and sends the two moment granules.
+// Lines of the part that are not walked (invalid, beyond the view's lines) send what their rows hold, for every field.
+// The chains run in uniform control flow (a DPP source lane that is switched off reads as 0); walked or not is a select.
+// No barrier: a row reads what phase B left behind its barrier and its own registers.
+// ---------------------------------------------------------------------------
+template <int DL>
+__device__ __forceinline__ float row_chain(float term, int dl) {  // lane dl - 1: the ordered sum of the row's terms
+  float acc = 0.0f + term;
+  if constexpr (DL > 0) {
+#pragma unroll
+    for (int k = 1; k < DL; ++k) acc = dpp_zero<0x111, 0xf>(acc) + term;
+  } else {
+    for (int k = 1; k < dl; ++k) acc = dpp_zero<0x111, 0xf>(acc) + term;
   }
+  return acc;
+}
+__device__ __forceinline__ float row_broadcast(float v, int src_lane) {  // byte address of the source lane: ds_bpermute
+  return __int_as_float(__builtin_amdgcn_ds_bpermute(src_lane << 2, __float_as_int(v)));
+}
+template <int DL>
+__device__ __forceinline__ void region_distribution_rows_dl(const SplitExchange& x, int round, CRegion& m, const Lds& s,
+                                                            int line_lo, int line_hi, const RegionWalked& w, int dl) {
+  const int tid = threadIdx.x, nt = blockDim.x, nl = s.nl, ns = s.ns;
+  const int fl = m.function_length;
+  const int lshift = x.lshift;
+  const int last = m3t_dist_rows_last(line_hi, nl);
+  const int rows = m3t_dist_rows_per_trip(nt);
+  const int d = m3t_dist_rows_lane(tid);
+  const bool lane_on = d < dl;
+  const int dr = lane_on ? d : 0;  // (idle lanes read value 0's operands: in bounds, never used)
+  const float fd = (float)d;
+  const int last_lane = (tid & (kWave - M3T_DIST_ROW_LANES)) + dl - 1;  // of this row, within the wave
+  auto* mine = x.granules + (((size_t)(round & 1) * x.n_parts + x.part) << (kExchangeFieldBits + lshift));
+  const unsigned long long tag_bits = static_cast<unsigned long long>(x.seq * 64u + (uint32_t)round + 1u) << 32;
+  const float mean_offset = m.distribution_length_minus_1_half, min_var = m.min_expected_variance;
+  const float* lf = s.misc + kMiscLookup;
+  const float* lb = s.misc + kMiscLookup + M3T_MAX_FUNCTION_LENGTH;
+  float lfr[8], lbr[8];
+  if (fl == 8) {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) { lfr[k] = m.function_lookup_f[k]; lbr[k] = m.function_lookup_b[k]; }
+  }
+  // (the wave's trips end with its first row: wave-uniform, the chains need every lane of a row)
+  for (int line = m3t_dist_rows_line(tid, 0, line_lo, nt);
+       __builtin_amdgcn_readfirstlane(m3t_dist_rows_wave_line(line, tid)) < last; line += rows) {
+    const bool row_on = line < last;
+    const int lr = row_on ? line : last - 1;  // (a row beyond the part: reads in bounds, nothing stored or sent)
+    const int flags = f2i_bits(s.state[LS_VALID * nl + lr]);
+    const bool walked = lr < w.n_lines_b && (flags & w.valid_mask);
+    const float* sf = s.seg_f + lr * ns + dr;
+    const float* sb = s.seg_b + lr * ns + dr;
+    float raw = 1.0f;
+    if (fl == 8) {  // default function_length: lookups as uniform scalars, independent LDS reads, ordered product
+      float f[8], b[8];
+#pragma unroll
+      for (int k = 0; k < 8; ++k) { f[k] = sf[k]; b[k] = sb[k]; }
+#pragma unroll
+      for (int k = 0; k < 8; ++k) raw *= f[k] * lfr[k] + b[k] * lbr[k];
+    } else {
+      for (int k = 0; k < fl; ++k) raw *= sf[k] * lf[k] + sb[k] * lb[k];
+    }
+    const float area = row_broadcast(row_chain<DL>(raw, dl), last_lane);
+    float value = raw / area;
+    if (!walked) value = s.state[(LS_DIST0 + dr) * nl + lr];  // what the row holds
+    if (row_on && lane_on) {
+      if (walked) s.state[(LS_DIST0 + d) * nl + line] = value;
+      __hip_atomic_store(mine + ((d << lshift) | (line - line_lo)), tag_bits | (unsigned)__float_as_int(value),
+                         __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    const float mean_from_begin = row_broadcast(row_chain<DL>(fd * value, dl), last_lane);
+    const float dd = fd - mean_from_begin;
+    const float var = row_chain<DL>((dd * dd) * value, dl);
+    if (row_on && d == dl - 1) {
+      float mean_out, var_out;
+      if (walked) {
+        mean_out = mean_from_begin - mean_offset;
+        var_out = fmaxf(var, min_var);
+        s.state[LS_MEAN * nl + line] = mean_out;
+        s.state[LS_VAR * nl + line] = var_out;
+      } else {
+        mean_out = s.state[LS_MEAN * nl + line];
+        var_out = s.state[LS_VAR * nl + line];
+      }
+      __hip_atomic_store(mine + ((dl << lshift) | (line - line_lo)), tag_bits | (unsigned)__float_as_int(mean_out),
+                         __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_store(mine + (((dl + 1) << lshift) | (line - line_lo)), tag_bits | (unsigned)__float_as_int(var_out),
+                         __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+  }
+}
+__device__ __forceinline__ void region_distribution_rows(const SplitExchange& x, int round, CRegion& m, const Lds& s,
+                                                         int line_lo, int line_hi, const RegionWalked& w) {
+  static_assert(M3T_DIST_ROW_LANES == M3T_MAX_DISTRIBUTION_LENGTH && kWave % M3T_DIST_ROW_LANES == 0, "a line per row");
+  const int dl = m.distribution_length;
+  if (dl == 12) region_distribution_rows_dl<12>(x, round, m, s, line_lo, line_hi, w, dl);  // the default length: unrolled
+  else region_distribution_rows_dl<0>(x, round, m, s, line_lo, line_hi, w, dl);
 }
 // what a waiting thread does with a granule that has not arrived: poll it again, give up after ~5 ms or when another
 // workgroup of the object has (split_exchange_collect's wait, as a function for the two collects below; they read
@@ -3202,8 +3306,8 @@ extern "C++" {
 // each in the reference's order, added like Link::CalculateGradientAndHessian adds them.  A template parameter, not a
 // run-time choice: the Region-only step keeps its machine code (with the choice inside, tracking_step_split_kernel went
 // from 234 to 241 VGPRs and the 64-object headline from 0.149 to 0.151 ms).
-// MOMENTS_FIRST (tracking_step_split_moments_kernel): the moments-first exchange (split_exchange_publish_moments and what
-// follows it) -- a template parameter for the same reason.
+// MOMENTS_FIRST (tracking_step_split_moments_kernel): the row pass (region_distribution_rows) and the moments-first
+// exchange behind it -- a template parameter for the same reason.
 template <bool HIST_LDS, bool SPLIT = false, bool RENDER = !SPLIT, bool GUARD = false, bool PAIR = false,
           bool MOMENTS_FIRST = false>
 __device__ __forceinline__ void tracking_step_body(const RigidOptDev* opts, const RegionModDev* rmods, const DepthModDev* dmods,
@@ -3296,13 +3400,20 @@ __device__ __forceinline__ void tracking_step_body(const RigidOptDev* opts, cons
     {
       const Affine b2w = load_pose(pose);
       bool vote_deferred = false;  // decided by region_correspondences (the one predicate for both sides)
+      RegionWalked walked{};       // (MOMENTS_FIRST: what the row pass needs of the search)
       if (rm) {
         const Affine b2c = mul_pose(load_pose(cam->world2camera), b2w);
         Affine b2dc = b2c;
         if (rdcam) b2dc = mul_pose(load_pose(rdcam->world2camera), b2w);
+        if constexpr (MOMENTS_FIRST) {  // (leaves behind phase B: region_distribution_rows below)
+          region_view = region_correspondences<HIST_LDS, 2, RENDER, false, true>(*rm, *cam, rdcam, b2c, b2dc, iteration, c, s,
+                                                                                 line_lo, line_hi, &vote_deferred,
+                                                                                 region_view, &exchange, &walked);
+        } else {
         region_view = region_correspondences<HIST_LDS, SPLIT ? 2 : 8, RENDER>(*rm, *cam, rdcam, b2c, b2dc, iteration, c, s,
                                                                               line_lo, line_hi, &vote_deferred, region_view,
                                                                               SPLIT ? &exchange : nullptr);
+        }
       }
       if (dm) {
         PHASE_T0();
@@ -3316,9 +3427,10 @@ __device__ __forceinline__ void tracking_step_body(const RigidOptDev* opts, cons
         // (the host vouches: Region-only, no occlusion pass, n_global_iterations >= 1)
         PHASE_T0();
         EXCHANGE_STAMP(0, c, part, object);
-        split_exchange_publish_moments(exchange, c, *rm, s, line_lo, line_hi);
+        // distributions, moments and their granules of the own lines: row by row, no barrier of its own
+        region_distribution_rows(exchange, c, *rm, s, line_lo, line_hi, walked);
         EXCHANGE_STAMP(1, c, part, object);
-        PHASE_MARK(30);  // owner moments
+        PHASE_MARK(33);  // the row pass (in place of phases C1, C2 and the owner moments, row 30)
         if (!split_exchange_collect_moments(exchange, c, *rm, s)) return;
         EXCHANGE_STAMP(2, c, part, object);
         PHASE_MARK(31);  // moments wait

@@ -4,7 +4,9 @@ publish = stamp(published) - stamp(publish start), wait = stamp(collected) - sta
 differ between CUs: only differences of one part's own stamps mean anything.)
 tracking_step_split_kernel: publish = what phase C2 has not sent yet, wait = the own lines' moments + the round trip of the
 distribution rows + the barrier.  tracking_step_split_moments_kernel (the line below names the launch): publish = the
-own lines' moments and their two granules per line, wait = the round trip of the means and variances + the barrier; the
+row pass (region_distribution_rows: from the barrier behind the pixel walk, the own lines' distributions, moments and all
+their granules; in a library from before the pass only the own lines' moments and their two granules per line, phases C1
+and C2 lying in front of the first stamp), wait = the round trip of the means and variances + the barrier; the
 distribution rows are collected beside the first Newton step and show up in "collected -> next publish start" only if
 they are late.
   python tools/exchange_waits.py <lib> [objects]"""

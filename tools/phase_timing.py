@@ -38,9 +38,12 @@ names = ["view search", "phase A (lines)", "phase B (pixels)", "phase C1 (dist)"
 # rows 27-29: the tail's parts (printed below).  Moments-first exchange (tracking_step_split_moments_kernel), in place of
 # "split exchange" and "moments / depth vote"; the deferred collect runs on another wave BESIDE the chain and the solve
 # (from the barrier behind the products of u = 0 to its last granule) and is not part of the total
+# Row 33: the row pass of tracking_step_split_moments_kernel (region_distribution_rows) -- distributions, moments and their
+# granules row by row, in place of "phase C1", "phase C2" and "owner moments" (rows 3, 4 and 30: their sum in a library
+# from before the pass is what row 33 compares with)
 extra = {30: "owner moments + their granules", 31: "moments wait (round trip + barrier)",
-         32: "  deferred collect (collecting wave)"}
-tot = sum(buf[i] for i in range(7)) + buf[16] + sum(buf[22:27]) + buf[30] + buf[31]
+         32: "  deferred collect (collecting wave)", 33: "row pass (dist + moments + granules)"}
+tot = sum(buf[i] for i in range(7)) + buf[16] + sum(buf[22:27]) + buf[30] + buf[31] + buf[33]
 for i, nme in enumerate(names):
     print("%-38s %10.0f cycles/frame  %5.1f%%" % (nme, buf[i] / n, 100.0 * buf[i] / tot))
 for i, nme in sorted(extra.items()):
