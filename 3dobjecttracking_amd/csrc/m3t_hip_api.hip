@@ -7,6 +7,7 @@
 #include <rccl/rccl.h>  // types only: the library is opened with dlopen when a structure spans GPUs
 
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -24,6 +25,7 @@
 #include "m3t_view_rows.h"
 #include "m3t_kernels.hip"
 #include "m3t_judge.hip"
+#include "m3t_opt.hip"
 #include "m3t_compact.hip"
 #include "m3t_render.hip"
 #include "m3t_modelgen.hip"
@@ -181,6 +183,12 @@ struct Judge {  // m3t_hip_judge_*: the evaluators' judgement of a list of bodie
   DevMem d_bodies, d_parts, d_flags, d_partial;
   int n_parts = 0, queries_per_thread = 1;
   bool any_split = false;
+  // m3t_hip_judge_set_add_only: the bodies judged as OPTEvaluator::CalculatePoseResults judges, by kernels of their own
+  std::vector<char> add_only;                      // per listed body
+  std::vector<std::array<float, 12>> geometry2body;  // per listed body, column-major 3 x 4
+  DevMem d_add_bodies, d_add_parts, d_add_partial;
+  int n_add_bodies = 0, n_add_parts = 0;
+  bool any_add_split = false;
   m3t_body_judgement* rows_host = nullptr;  // [n_rows_max][n_bodies], written by the kernels in place
   m3t_body_judgement* rows_dev = nullptr;
   std::vector<hipEvent_t> row_done;         // per row: behind the launches of its call
@@ -4024,29 +4032,59 @@ int BuildJudgeTables(Ctx* ctx, Judge* j) {
   HIPCHK(hipStreamSynchronize(ctx->stream));
   const int n = int(j->body_ids.size());
   long chunks = 0;
-  for (int v : j->n_vertices) chunks += std::max(1, (v + M3T_JUDGE_SPLIT_QUERIES - 1) / M3T_JUDGE_SPLIT_QUERIES);
+  for (int i = 0; i < n; ++i)
+    if (!j->add_only[size_t(i)])
+      chunks += std::max(1, (j->n_vertices[size_t(i)] + M3T_JUDGE_SPLIT_QUERIES - 1) / M3T_JUDGE_SPLIT_QUERIES);
   j->queries_per_thread = chunks > 4L * std::max(1, ctx->prop.multiProcessorCount) ? 4 : 1;
   const int q = j->queries_per_thread * M3T_JUDGE_THREADS;
   std::vector<JudgeBodyDev> bodies(static_cast<size_t>(n));
   std::vector<JudgePartDev> parts;
-  j->any_split = false;
+  std::vector<JudgeAddBodyDev> add_bodies;
+  std::vector<JudgePartDev> add_parts;
+  j->any_split = j->any_add_split = false;
   for (int i = 0; i < n; ++i) {
     JudgeBodyDev& b = bodies[size_t(i)];
     b.vertices = j->vertices[size_t(i)] ? j->vertices[size_t(i)]->as<float4>() : nullptr;
     b.body = j->body_ids[size_t(i)];
     b.n_vertices = j->n_vertices[size_t(i)];
     b.first_part = int(parts.size());
+    if (j->add_only[size_t(i)]) {  // no workgroup of judge_bodies_kernel, nothing for judge_finish_kernel
+      b.n_parts = 1;
+      JudgeAddBodyDev a;
+      a.vertices = b.vertices;
+      a.index = i;
+      a.body = b.body;
+      a.n_vertices = b.n_vertices;
+      a.first_part = int(add_parts.size());
+      a.n_parts = std::max(1, (a.n_vertices + M3T_JUDGE_ADD_SPLIT - 1) / M3T_JUDGE_ADD_SPLIT);
+      std::memcpy(a.geometry2body, j->geometry2body[size_t(i)].data(), sizeof(a.geometry2body));
+      j->any_add_split = j->any_add_split || a.n_parts > 1;
+      for (int p = 0; p < a.n_parts; ++p) add_parts.push_back(JudgePartDev{int(add_bodies.size()), p});
+      add_bodies.push_back(a);
+      continue;
+    }
     b.n_parts = std::max(1, (b.n_vertices + q - 1) / q);
     j->any_split = j->any_split || b.n_parts > 1;
     for (int p = 0; p < b.n_parts; ++p) parts.push_back(JudgePartDev{i, p});
   }
   j->n_parts = int(parts.size());
+  j->n_add_bodies = int(add_bodies.size());
+  j->n_add_parts = int(add_parts.size());
   HIPCHK(j->d_bodies.alloc(bodies.size() * sizeof(JudgeBodyDev)));
-  HIPCHK(j->d_parts.alloc(parts.size() * sizeof(JudgePartDev)));
-  HIPCHK(j->d_partial.alloc(parts.size() * 2 * sizeof(double)));
+  HIPCHK(j->d_parts.alloc(std::max<size_t>(1, parts.size()) * sizeof(JudgePartDev)));
+  HIPCHK(j->d_partial.alloc(std::max<size_t>(1, parts.size()) * 2 * sizeof(double)));
   HIPCHK(j->d_flags.alloc(size_t(n) * sizeof(int)));
   HIPCHK(hipMemcpy(j->d_bodies.p, bodies.data(), bodies.size() * sizeof(JudgeBodyDev), hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(j->d_parts.p, parts.data(), parts.size() * sizeof(JudgePartDev), hipMemcpyHostToDevice));
+  if (!parts.empty())
+    HIPCHK(hipMemcpy(j->d_parts.p, parts.data(), parts.size() * sizeof(JudgePartDev), hipMemcpyHostToDevice));
+  if (!add_bodies.empty()) {
+    HIPCHK(j->d_add_bodies.alloc(add_bodies.size() * sizeof(JudgeAddBodyDev)));
+    HIPCHK(j->d_add_parts.alloc(add_parts.size() * sizeof(JudgePartDev)));
+    HIPCHK(j->d_add_partial.alloc(add_parts.size() * sizeof(double)));
+    HIPCHK(hipMemcpy(j->d_add_bodies.p, add_bodies.data(), add_bodies.size() * sizeof(JudgeAddBodyDev),
+                     hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(j->d_add_parts.p, add_parts.data(), add_parts.size() * sizeof(JudgePartDev), hipMemcpyHostToDevice));
+  }
   HIPCHK(hipMemset(j->d_flags.p, 0, size_t(n) * sizeof(int)));
   return M3T_OK;
 }
@@ -4072,6 +4110,8 @@ int m3t_hip_judge_create(m3t_hip_context* ctx, const int* body_ids, int n_bodies
   j->n_rows_max = n_rows_max;
   j->n_vertices.assign(size_t(n_bodies), 0);
   j->vertices.resize(size_t(n_bodies));
+  j->add_only.assign(size_t(n_bodies), 0);
+  j->geometry2body.resize(size_t(n_bodies));
   j->row_done.assign(size_t(n_rows_max), nullptr);
   const size_t bytes = size_t(n_bodies) * size_t(n_rows_max) * sizeof(m3t_body_judgement);
   HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&j->rows_host), bytes, hipHostMallocMapped));
@@ -4206,6 +4246,18 @@ int m3t_hip_judge_bodies(m3t_hip_context* ctx, int judge, const float* gt_body2w
   m3t_body_judgement* d_row = j->rows_dev + size_t(row_index) * size_t(n);
   if (!j->row_done[size_t(row_index)])
     HIPCHK(hipEventCreateWithFlags(&j->row_done[size_t(row_index)], hipEventDisableTiming));
+  if (j->n_add_parts > 0) {  // the ADD-only bodies: workgroups of their own (m3t_opt.hip)
+    hipLaunchKernelGGL(judge_add_only_kernel, dim3(unsigned(j->n_add_parts)), dim3(M3T_JUDGE_THREADS), 0, ctx->stream,
+                       ctx->d_poses.as<float>(), j->d_add_bodies.as<JudgeAddBodyDev>(), j->d_add_parts.as<JudgePartDev>(),
+                       d_gt, j->thr_t, j->thr_r, reset_iteration, ctx->d_region.as<RegionModDev>(), d_region_ids,
+                       d_region_first, j->d_flags.as<int>(), d_row, j->d_add_partial.as<double>());
+    if (j->any_add_split)
+      hipLaunchKernelGGL(judge_add_only_finish_kernel, dim3(unsigned(j->n_add_bodies)), dim3(64), 0, ctx->stream,
+                         ctx->d_poses.as<float>(), j->d_add_bodies.as<JudgeAddBodyDev>(), d_gt, reset_iteration,
+                         ctx->d_region.as<RegionModDev>(), d_region_ids, d_region_first, j->d_flags.as<int>(), d_row,
+                         j->d_add_partial.as<double>());
+  }
+  if (j->n_parts > 0)
   hipLaunchKernelGGL(j->queries_per_thread == 4 ? judge_bodies_x4_kernel : judge_bodies_kernel, dim3(unsigned(j->n_parts)),
                      dim3(M3T_JUDGE_THREADS), 0, ctx->stream, ctx->d_poses.as<float>(), j->d_bodies.as<JudgeBodyDev>(),
                      j->d_parts.as<JudgePartDev>(), d_gt, j->thr_t, j->thr_r, reset_iteration,
@@ -4323,6 +4375,68 @@ int m3t_hip_judge_read_structures(m3t_hip_context* ctx, int judge, int first_row
   HIPCHK(hipEventSynchronize(j->row_done[size_t(first_row + n_rows - 1)]));  // rows complete in order
   const size_t n = size_t(j->n_structures);
   std::memcpy(out, j->structure_rows_host + size_t(first_row) * n, size_t(n_rows) * n * sizeof(m3t_structure_judgement));
+  return M3T_OK;
+}
+// OPTEvaluator::CalculatePoseResults for listed body `index` from now on (m3t_hip.h).  Waits for the stream and uploads:
+// outside the frame loop, like judge_set_vertices.
+int m3t_hip_judge_set_add_only(m3t_hip_context* ctx, int judge, int index, const float* geometry2body_pose) {
+  CHECK_CTX();
+  REQUIRE(judge >= 0 && judge < int(ctx->judges.size()), M3T_ERR_INVALID_ARGUMENT, "judge_set_add_only: bad judge id");
+  Judge* j = ctx->judges[size_t(judge)].get();
+  REQUIRE(index >= 0 && index < int(j->body_ids.size()), M3T_ERR_INVALID_ARGUMENT, "judge_set_add_only: bad body index");
+  REQUIRE(j->n_rows == 0, M3T_ERR_INVALID_ARGUMENT, "judge_set_add_only: rows have been judged already (judge_clear first)");
+  std::array<float, 12> g = {1.0f, 0.0f, 0.0f, 0.0f, 1.0f, 0.0f, 0.0f, 0.0f, 1.0f, 0.0f, 0.0f, 0.0f};
+  if (geometry2body_pose) {
+    for (int i = 0; i < 16; ++i)
+      REQUIRE(std::isfinite(geometry2body_pose[i]), M3T_ERR_INVALID_ARGUMENT,
+              "judge_set_add_only: a non-finite entry in geometry2body_pose");
+    for (int c = 0; c < 4; ++c)
+      for (int r = 0; r < 3; ++r) g[size_t(3 * c + r)] = geometry2body_pose[4 * c + r];
+  }
+  HIPCHK(hipSetDevice(ctx->device));
+  j->add_only[size_t(index)] = 1;
+  j->geometry2body[size_t(index)] = g;
+  return BuildJudgeTables(ctx, j);
+}
+// OPTEvaluator::CalculateDiameters (opt_evaluator.cpp:580-600) of one vertex set (m3t_hip.h).  Waits for the stream,
+// uploads and waits for the result: outside the frame loop.  Touches nothing of the tracking state.
+int m3t_hip_vertices_diameter(m3t_hip_context* ctx, const float* xyz, int n_vertices, float* diameter) {
+  CHECK_CTX();
+  REQUIRE(n_vertices >= 1 && n_vertices <= (1 << 20), M3T_ERR_INVALID_ARGUMENT, "vertices_diameter: 1 to 2^20 vertices");
+  REQUIRE(xyz && diameter, M3T_ERR_INVALID_ARGUMENT, "vertices_diameter: null vertices or result");
+  for (size_t i = 0; i < size_t(n_vertices) * 3; ++i)  // fmaxf would drop a NaN silently
+    REQUIRE(std::isfinite(xyz[i]), M3T_ERR_INVALID_ARGUMENT, "vertices_diameter: a non-finite coordinate");
+  if (n_vertices == 1) {
+    *diameter = 0.0f;
+    return M3T_OK;
+  }
+  HIPCHK(hipSetDevice(ctx->device));
+  const size_t n_tiles = (size_t(n_vertices) + M3T_DIAMETER_TILE - 1) / M3T_DIAMETER_TILE;
+  const size_t n_padded = n_tiles * M3T_DIAMETER_TILE;
+  std::vector<float> padded(n_padded * 4, 0.0f);
+  for (size_t i = 0; i < n_padded; ++i) {
+    const float* v = xyz + 3 * (i < size_t(n_vertices) ? i : 0);  // a copy of vertex 0 forms pairs of the set only
+    padded[4 * i] = v[0];
+    padded[4 * i + 1] = v[1];
+    padded[4 * i + 2] = v[2];
+  }
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  DevMem vertices, max_bits;
+  HIPCHK(vertices.alloc(padded.size() * 4));
+  HIPCHK(max_bits.alloc(sizeof(unsigned int)));
+  HIPCHK(hipMemcpy(vertices.p, padded.data(), padded.size() * 4, hipMemcpyHostToDevice));
+  HIPCHK(hipMemset(max_bits.p, 0, sizeof(unsigned int)));
+  for (size_t first = 0; first < n_tiles; first += M3T_DIAMETER_ROW_TILES_PER_LAUNCH) {
+    ScopedKernelTimer timer(ctx, 1);
+    const size_t rows = std::min<size_t>(M3T_DIAMETER_ROW_TILES_PER_LAUNCH, n_tiles - first);
+    hipLaunchKernelGGL(vertices_diameter_kernel, dim3(unsigned(n_tiles), unsigned(rows)), dim3(M3T_DIAMETER_THREADS), 0,
+                       ctx->stream, vertices.as<float4>(), int(first), max_bits.as<unsigned int>());
+  }
+  HIPCHK(hipGetLastError());
+  float d2 = 0.0f;
+  HIPCHK(hipMemcpyAsync(&d2, max_bits.p, sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  *diameter = sqrtf(d2);
   return M3T_OK;
 }
 int m3t_hip_judge_clear(m3t_hip_context* ctx, int judge) {

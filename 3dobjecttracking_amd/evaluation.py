@@ -4,7 +4,8 @@ RBOT (M3T/examples/rbot_evaluator.cpp): ground-truth pose file reader, the 5 cm 
 the frame loop with reset-on-loss.  YCB-Video (M3T/examples/ycb_evaluator.cpp): ground-truth reader, ADD /
 ADD-S per frame, the tracking-loss curves and the area under curve, reduced evaluation vertices.  The
 datasets themselves are external downloads; the loops take a frame source, so that synthetic sequences and
-the real datasets run through the same code.
+the real datasets run through the same code.  OPT (M3T/examples/opt_evaluator.cpp): ground-truth reader, ADD per frame
+against the body's diameter, computed diameters, N sequences of different lengths in one context.
 """
 import time
 
@@ -775,3 +776,344 @@ def evaluate_ycb_dataset(open_context, dataset_directory, external_directory, se
                    adds_auc=float(np.mean([r["adds_auc"] for r in frame_results])),
                    complete_cycle=float(np.mean([r["complete_cycle"] for r in frame_results])))
     return results, overall
+
+
+# ---------------------------------------------------------------------------------------------------------
+# OPT (M3T/examples/opt_evaluator.cpp + evaluate_opt_dataset.cpp): Region + Depth, single bodies
+# ---------------------------------------------------------------------------------------------------------
+OPT_N_CURVE_VALUES = 100  # opt_evaluator.h:41
+OPT_THRESHOLD_MAX = 0.2   # opt_evaluator.h:42
+OPT_INTRINSICS = (1060.197, 1060.273, 964.809, 560.952, 1920, 1080)  # opt_evaluator.h:43-44
+OPT_DEPTH2COLOR_POSE = np.asarray([[0.9999788893, -0.0052817802, 0.0037846718, -0.0525133559],  # opt_evaluator.h:45-49
+                                   [0.0052971168, 0.9999777534, -0.0040537989, 0.0006022050],
+                                   [-0.0037631764, 0.0040737612, 0.9999846214, -0.0003262078],
+                                   [0.0, 0.0, 0.0, 1.0]], F)
+OPT_GEOMETRY2BODY_TRANSLATIONS = dict(  # opt_evaluator.h:50-63 (kBody2Geometry2BodyPoseMap: pure translations)
+    soda=(0.0006, -0.0004, -0.0549), chest=(-0.0002, -0.0009, -0.0377), ironman=(0.0023, 0.0005, -0.0506),
+    house=(-0.0008, -0.0059, -0.0271), bike=(-0.0018, 0.0001, -0.0267), jet=(-0.0004, 0.0001, -0.0117))
+OPT_BODY_NAMES = ("soda", "chest", "ironman", "house", "bike", "jet")  # evaluate_opt_dataset.cpp:13-14
+OPT_BODY_ORIENTATIONS = ("b", "f", "l", "r")                           # :15
+OPT_MOTION_PATTERNS = ("tr_1", "tr_2", "tr_3", "tr_4", "tr_5", "zo_1", "zo_2", "zo_3", "zo_4", "zo_5", "ir_1", "ir_2",
+                       "ir_3", "ir_4", "ir_5", "or_1", "or_2", "or_3", "or_4", "or_5", "fl", "ml", "fm")  # :16-19
+OPT_REGION_PARAMETERS = dict(  # evaluate_opt_dataset.cpp:24-40
+    n_lines_max=200, use_adaptive_coverage=0, min_continuous_distance=3.0, function_length=8, distribution_length=12,
+    function_amplitude=0.43, function_slope=0.5, learning_rate=1.3, scales=[6, 4, 1],
+    standard_deviations=[15.0, 5.0, 1.5], n_histogram_bins=16, learning_rate_f=0.2, learning_rate_b=0.2,
+    unconsidered_line_length=0.5, max_considered_line_length=20.0)
+OPT_DEPTH_PARAMETERS = dict(  # evaluate_opt_dataset.cpp:41-48
+    n_points_max=200, use_adaptive_coverage=0, use_depth_scaling=0, stride_length=0.005,
+    considered_distances=[0.05, 0.02, 0.01], standard_deviations=[0.035, 0.035, 0.025])
+OPT_MODEL_PARAMETERS = dict(sphere_radius=0.8, n_divides=4, n_points=500, max_radius_depth_offset=0.05,
+                            stride_depth_offset=0.002, use_random_seed=False, image_size=2000)  # opt_evaluator.cpp:531-543
+OPT_TIKHONOV_PARAMETER_ROTATION = 1000.0      # evaluate_opt_dataset.cpp:78-79
+OPT_TIKHONOV_PARAMETER_TRANSLATION = 30000.0  # :80
+OPT_N_UPDATE_ITERATIONS = 2                   # :85
+OPT_N_CORR_ITERATIONS = 4                     # :86
+OPT_DEPTH_SCALE = 0.001                       # opt_evaluator.cpp:267
+
+
+def opt_geometry2body_pose(body_name):
+    """kBody2Geometry2BodyPoseMap.at(body_name) (opt_evaluator.h:50-63)"""
+    pose = np.eye(4, dtype=F)
+    pose[:3, 3] = OPT_GEOMETRY2BODY_TRANSLATIONS[body_name]
+    return pose
+
+
+def opt_sequence_name(body_name, body_orientation, motion_pattern):
+    """CreateRunConfigurations (opt_evaluator.cpp:499-511)"""
+    return body_name[:2] + "_" + motion_pattern + "_" + body_orientation
+
+
+def opt_thresholds():
+    """opt_evaluator.cpp:19-22"""
+    step = F(OPT_THRESHOLD_MAX) / F(OPT_N_CURVE_VALUES)
+    return np.asarray([step * (F(0.5) + F(i)) for i in range(OPT_N_CURVE_VALUES)], F)
+
+
+def read_poses_opt(path, geometry2body):
+    """OPTEvaluator::GetGTPosesOPTDataset (opt_evaluator.cpp:602-630): one pose per line, twelve numbers separated by
+    blanks, filled as matrix(j, i) for i in 0..3 and j in 0..2 (column by column, the translation last), then
+    pose * geometry2body^-1 in f32"""
+    inverse = _inverse_pose_f32(np.asarray(geometry2body, F).reshape(4, 4))
+    poses = []
+    with open(path) as f:
+        for line in f:
+            if not line.strip():
+                continue
+            t = line.split(" ")
+            pose = np.eye(4, dtype=F)
+            for i in range(4):
+                for j in range(3):
+                    pose[j, i] = F(t[3 * i + j])
+            poses.append(_mul_pose_f32(pose, inverse))
+    return np.asarray(poses, F).reshape(-1, 4, 4)
+
+
+def opt_delta_pose(body2world_pose, gt_body2world_pose, geometry2body):
+    """(body2world * geometry2body)^-1 * gt * geometry2body (opt_evaluator.cpp:466-468) as the device judge forms it
+    (m3t_hip_judge_set_add_only): f64, left to right, the rigid inverse [R^T | -R^T t], every sum left to right,
+    rounded to f32 once.  Returns the 3 x 4 matrix."""
+    p = [[float(v) for v in row] for row in np.asarray(body2world_pose, F).reshape(4, 4)]
+    t = [[float(v) for v in row] for row in np.asarray(gt_body2world_pose, F).reshape(4, 4)]
+    g = [[float(v) for v in row] for row in np.asarray(geometry2body, F).reshape(4, 4)]
+    a = [[(p[r][0] * g[0][c] + p[r][1] * g[1][c]) + p[r][2] * g[2][c] + (p[r][3] if c == 3 else 0.0)
+          for c in range(4)] for r in range(3)]
+    delta = np.zeros((3, 4), F)
+    for r in range(3):
+        i0, i1, i2 = a[0][r], a[1][r], a[2][r]
+        i3 = -((i0 * a[0][3] + i1 * a[1][3]) + i2 * a[2][3])
+        m = [((i0 * t[0][k] + i1 * t[1][k]) + i2 * t[2][k]) + i3 * t[3][k] for k in range(4)]
+        for c in range(4):
+            v = (m[0] * g[0][c] + m[1] * g[1][c]) + m[2] * g[2][c]
+            delta[r, c] = F(v + m[3] if c == 3 else v)
+    return delta
+
+
+def vertices_diameter(api, vertices, chunk=512):
+    """OPTEvaluator::CalculateDiameters (opt_evaluator.cpp:580-600): the largest distance between two vertices, by
+    exhaustive search -- m3t_hip_vertices_diameter on the HIP library, elsewhere the same arithmetic in numpy, chunk
+    rows at a time: per pair d2 = (dx*dx + dy*dy) + dz*dz in f32, the diameter the f32 root of the largest"""
+    v = np.ascontiguousarray(vertices, F).reshape(-1, 3)
+    if api is not None and "vertices_diameter" in api._fn:
+        import ctypes as C
+        out = C.c_float(0.0)
+        api.call("vertices_diameter", v.ctypes.data_as(C.POINTER(C.c_float)), len(v), C.byref(out))
+        return F(out.value)
+    if len(v) < 1 or not np.isfinite(v).all():
+        raise ValueError("vertices_diameter: needs at least one vertex and finite coordinates")
+    best = F(0.0)
+    x, y, z = v[:, 0], v[:, 1], v[:, 2]
+    for i in range(0, len(v), chunk):  # d2 is symmetric: the columns from the chunk's first row on
+        dx = x[i:i + chunk, None] - x[None, i:]
+        dy = y[i:i + chunk, None] - y[None, i:]
+        dz = z[i:i + chunk, None] - z[None, i:]
+        best = max(best, ((dx * dx + dy * dy) + dz * dz).max())
+    return F(np.sqrt(F(best)))
+
+
+class OPTBodyEvaluation:
+    """the per-body data of OPTEvaluator::CalculatePoseResults (opt_evaluator.cpp:462-488): the reduced vertices of
+    GenderateReducedVertices (:545-578; `vertices` as m3t::Body::vertices() holds them: the mesh's own, scaled,
+    geometry2body not applied -- what generator.Body.vertices holds), the geometry-to-body pose and the diameter"""
+
+    def __init__(self, vertices, geometry2body, diameter, n_vertices_evaluation=-1):
+        self.vertices = np.ascontiguousarray(reduce_vertices(vertices, n_vertices_evaluation), F)
+        self.geometry2body = np.asarray(geometry2body, F).reshape(4, 4)
+        self.diameter = F(diameter)
+        self.thresholds = opt_thresholds()
+
+    def error(self, body2world_pose, gt_body2world_pose):
+        """ADD in metres: the mean of |v - delta v|.  The reference forms delta and the sum in f32; this keeps the
+        arithmetic of the device judge (f64 delta rounded once, f32 per vertex, f64 sum), as YCBBodyEvaluation does"""
+        d = opt_delta_pose(body2world_pose, gt_body2world_pose, self.geometry2body)
+        x, y, z = self.vertices[:, 0], self.vertices[:, 1], self.vertices[:, 2]
+        ex = x - (((d[0, 0] * x + d[0, 1] * y) + d[0, 2] * z) + d[0, 3])
+        ey = y - (((d[1, 0] * x + d[1, 1] * y) + d[1, 2] * z) + d[1, 3])
+        ez = z - (((d[2, 0] * x + d[2, 1] * y) + d[2, 2] * z) + d[2, 3])
+        norms = np.sqrt((ex * ex + ey * ey) + ez * ez)
+        return float(F(norms.astype(np.float64).sum() / float(len(norms))))
+
+    def result(self, body2world_pose, gt_body2world_pose):
+        return self.result_of_error(self.error(body2world_pose, gt_body2world_pose))
+
+    def result_of_error(self, add):
+        """curve and area under curve from ADD in metres (judged here or on the device), :475-487 in f32"""
+        error = F(add)
+        curve = np.ones(OPT_N_CURVE_VALUES, F)
+        for i in range(OPT_N_CURVE_VALUES):
+            if error < F(self.diameter * self.thresholds[i]):
+                break
+            curve[i] = 0.0
+        threshold = F(self.diameter * F(OPT_THRESHOLD_MAX))
+        auc = F(F(OPT_THRESHOLD_MAX) * F(F(1.0) - min(F(error / threshold), F(1.0))))
+        return dict(add_error=float(error), curve_values=curve, area_under_curve=float(auc))
+
+
+def evaluate_opt_sequences(tracker, bodies, evaluations, gt_poses_per_body, load_images, judge_on_device=False):
+    """The loop of OPTEvaluator::EvaluateRunConfiguration (opt_evaluator.cpp:204-251) for S independent bodies in ONE
+    context, each with a list of sequences of its own: gt_poses_per_body[s][q][k] is the ground-truth pose of body s in
+    image k of its sequence q.  A body starts a sequence on image 0 at its ground truth (:217-218); cycle i tracks image
+    i + 1 and is judged against its ground truth (CalculatePoseResults).  The sequences may have different lengths: a
+    body whose sequence has ended is put on the first pose of its next one with Tracker.ResetBodies while the others
+    keep tracking, so each body's results are those of a tracker of its own.  The step's iteration number is the
+    batch's cycle counter and a body's first_iteration the cycle it started on: their difference -- all the modalities
+    read -- is the sequence's own cycle index.  `load_images(s, q, k)` makes image k of sequence q current in the
+    cameras of body s.
+    A library without reset_bodies (the oracle) can only restart all bodies of the context together: one body, or
+    sequences of equal length.
+    judge_on_device (HIP library): one judge, every body ADD-only with its geometry2body (Judge.set_add_only),
+    judge(gt, -1) behind every step; no Sync() and no pose read per frame, the rows are read once at the end.
+    Returns results[s][q] = list of per-cycle dicts (frame_index, add_error, area_under_curve, curve_values)."""
+    n = len(bodies)
+    device_reset = "reset_bodies" in tracker.api._fn
+    results = [[[] for _ in sequences] for sequences in gt_poses_per_body]
+    state = [[0, 0] for _ in range(n)]  # sequence, cycle inside it
+
+    def start(which, iteration):
+        for s in which:
+            load_images(s, state[s][0], 0)
+        poses = [gt_poses_per_body[s][state[s][0]][0] for s in which]
+        if len(which) == n:  # all together: the reference's start (:217-218)
+            for s, pose in zip(which, poses):
+                bodies[s].set_body2world_pose(pose)
+            if not tracker.StartModalities(iteration):
+                raise RuntimeError("StartModalities failed")
+        elif device_reset:
+            if not tracker.ResetBodies([bodies[s] for s in which], poses, iteration):
+                raise RuntimeError("ResetBodies failed")
+        else:
+            raise RuntimeError("this library restarts all bodies of a context together (no reset_bodies)")
+
+    active = [s for s in range(n) if len(gt_poses_per_body[s]) > 0]
+    if len(active) != n:
+        raise ValueError("every body needs at least one sequence")
+    start(active, 0)
+    judge, pending = None, []
+    if judge_on_device:
+        total = max(sum(len(seq) - 1 for seq in sequences) for sequences in gt_poses_per_body)
+        judge = tracker.CreateJudge(bodies, max(1, total))
+        for s, evaluation in enumerate(evaluations):
+            judge.set_vertices(s, evaluation.vertices)
+            judge.set_add_only(s, evaluation.geometry2body)
+        last_gt = [gt_poses_per_body[s][0][0] for s in range(n)]
+    cycle = 0
+    while active:
+        for s in active:
+            load_images(s, state[s][0], state[s][1] + 1)
+        if not tracker.ExecuteTrackingStep(cycle):
+            raise RuntimeError("tracking step %d failed" % cycle)
+        if judge_on_device:
+            for s in active:
+                last_gt[s] = gt_poses_per_body[s][state[s][0]][state[s][1] + 1]
+            row = judge.judge(last_gt, -1)
+            pending += [(row, s, state[s][0], state[s][1]) for s in active]
+        else:
+            if not tracker.Sync():
+                raise RuntimeError("tracking step %d failed" % cycle)
+            for s in active:
+                q, i = state[s]
+                r = evaluations[s].result(bodies[s].body2world_pose(), gt_poses_per_body[s][q][i + 1])
+                r.update(frame_index=i)
+                results[s][q].append(r)
+        ended = []
+        for s in list(active):
+            state[s][1] += 1
+            if state[s][1] + 1 < len(gt_poses_per_body[s][state[s][0]]):
+                continue
+            state[s] = [state[s][0] + 1, 0]
+            if state[s][0] < len(gt_poses_per_body[s]):
+                ended.append(s)
+            else:
+                active.remove(s)
+        cycle += 1
+        if ended:
+            start(ended, cycle)
+    if judge_on_device and pending:
+        rows = judge.read(0, pending[-1][0] + 1)
+        for row, s, q, i in pending:
+            r = evaluations[s].result_of_error(float(rows[row, s]["add_error"]))
+            r.update(frame_index=i)
+            results[s][q].append(r)
+    return results
+
+
+def opt_average_result(frame_results):
+    """CalculateAverageResult / SumResults / DivideResult (opt_evaluator.cpp:402-460) over per-frame results, in f32"""
+    auc, curve = F(0.0), np.zeros(OPT_N_CURVE_VALUES, F)
+    for r in frame_results:
+        auc = F(auc + F(r["area_under_curve"]))
+        curve = (curve + r["curve_values"]).astype(F)
+    n = F(max(1, len(frame_results)))
+    return dict(area_under_curve=float(F(auc / n)), curve_values=(curve / n).astype(F))
+
+
+def evaluate_opt_dataset(open_context, dataset_directory, external_directory, body_names=OPT_BODY_NAMES,
+                         body_orientations=OPT_BODY_ORIENTATIONS, motion_patterns=OPT_MOTION_PATTERNS,
+                         region_parameters=None, depth_parameters=None, model_parameters=None,
+                         tikhonov_parameter_rotation=OPT_TIKHONOV_PARAMETER_ROTATION,
+                         tikhonov_parameter_translation=OPT_TIKHONOV_PARAMETER_TRANSLATION,
+                         n_corr_iterations=OPT_N_CORR_ITERATIONS, n_update_iterations=OPT_N_UPDATE_ITERATIONS,
+                         report=None, shard=(0, 1), batch=1, n_vertices_evaluation=1000, calculate_diameters=True,
+                         diameters=None, intrinsics=OPT_INTRINSICS, depth2color_pose=OPT_DEPTH2COLOR_POSE,
+                         judge_on_device=False):
+    """OPTEvaluator::SetUp + Evaluate in the Region + Depth configuration (set_use_texture_modality(false)): one run per
+    (body, orientation, motion pattern) (CreateRunConfigurations :499-511) on `dataset/3D/<sequence>/color|depth/
+    NNNN.png` from image 1 (loader cameras :261-271, depth scale 0.001, the depth camera's camera2world the
+    depth-to-colour pose), ground truth `dataset/3D/poses/<sequence>.txt`, bodies `dataset/Model3D/<body>/<body>.obj`
+    in metres with their geometry-to-body translations (LoadBodies :513-525), models under `external/models/`
+    (GenerateModels :527-553), ADD over n_vertices_evaluation reduced vertices against the body's diameter.
+    calculate_diameters: CalculateDiameters over all of a body's vertices (vertices_diameter: on the device with the
+    HIP library); otherwise `diameters` gives them by body name (the reference's table is not restated).
+    `intrinsics` and `depth2color_pose` default to the dataset's (a synthetic dataset brings its own).
+    batch: up to `batch` bodies share one context, each with its own cameras and its own list of this process's
+    sequences, through evaluate_opt_sequences (one body per context: batch = 1).  shard = (rank, world): every world-th
+    run.  Returns {sequence name: average result}, and the averages per body and over "all" bodies of all their frames
+    (CalculateAverageBodyResult :402-415)."""
+    import os
+
+    from . import config as cfg
+    from . import generator, host
+    region_parameters = dict(OPT_REGION_PARAMETERS, **(region_parameters or {}))
+    depth_parameters = dict(OPT_DEPTH_PARAMETERS, **(depth_parameters or {}))
+    model_parameters = dict(OPT_MODEL_PARAMETERS, **(model_parameters or {}))
+    generation = {k: v for k, v in model_parameters.items() if k != "use_random_seed"}
+    runs = [(name, opt_sequence_name(name, orientation, pattern)) for name in body_names
+            for orientation in body_orientations for pattern in motion_patterns][shard[0]::shard[1]]
+    per_body = {}
+    for name, sequence in runs:
+        per_body.setdefault(name, []).append(sequence)
+    names = list(per_body)
+    results, frames_of_body = {}, {name: [] for name in names}
+    for first in range(0, len(names), max(1, batch)):
+        chunk = names[first:first + max(1, batch)]
+        api = open_context()
+        bodies, evaluations, cameras, gt = [], [], [], []
+        for name in chunk:
+            geometry2body = opt_geometry2body_pose(name) if name in OPT_GEOMETRY2BODY_TRANSLATIONS else np.eye(4, dtype=F)
+            body = generator.Body(api, name, os.path.join(dataset_directory, "Model3D", name, name + ".obj"), 1.0, True,
+                                  True, geometry2body)
+            models = []
+            for region, klass, suffix in ((True, host.RegionModel, "_region_model.bin"),
+                                          (False, host.DepthModel, "_depth_model.bin")):
+                path = os.path.join(external_directory, "models", name + suffix)
+                if cfg.model_bin_matches(path, region, model_parameters, body.body_data()):
+                    models.append(klass(api, path=path))
+                else:
+                    models.append(klass.generate(api, body, **generation))
+                    cfg.write_model_bin(path, region, model_parameters, body.body_data(), *models[-1].views())
+            directory = os.path.join(dataset_directory, "3D", per_body[name][0])
+            color = generator.LoaderColorCamera(api, os.path.join(directory, "color"), intrinsics, "", 1, 4)
+            depth = generator.LoaderDepthCamera(api, os.path.join(directory, "depth"), intrinsics, OPT_DEPTH_SCALE, "", 1,
+                                                4, camera2world_pose=depth2color_pose)
+            region_modality = host.RegionModality(api, body, color, models[0], **region_parameters)
+            depth_modality = host.DepthModality(api, body, depth, models[1], **depth_parameters)
+            host.Optimizer(api, body=body, modalities=[region_modality, depth_modality],
+                           tikhonov_parameter_rotation=tikhonov_parameter_rotation,
+                           tikhonov_parameter_translation=tikhonov_parameter_translation)
+            diameter = vertices_diameter(api, body.vertices) if calculate_diameters else diameters[name]
+            bodies.append(body)
+            evaluations.append(OPTBodyEvaluation(body.vertices, geometry2body, diameter, n_vertices_evaluation))
+            cameras.append((color, depth))
+            gt.append([read_poses_opt(os.path.join(dataset_directory, "3D", "poses", sequence + ".txt"), geometry2body)
+                       for sequence in per_body[name]])
+        tracker = host.Tracker(api, n_corr_iterations, n_update_iterations)
+
+        def load_images(s, q, k, chunk=chunk, cameras=cameras):
+            directory = os.path.join(dataset_directory, "3D", per_body[chunk[s]][q])
+            for camera, kind in zip(cameras[s], ("color", "depth")):
+                camera.load_directory = os.path.join(directory, kind)
+                camera.set_load_index(1 + k)  # (drops what was prefetched from the last directory)
+                if not camera.UpdateImage():
+                    raise RuntimeError("Could not read image from %s" % camera.image_path())
+
+        per_sequence = evaluate_opt_sequences(tracker, bodies, evaluations, gt, load_images,
+                                              judge_on_device=judge_on_device)
+        for s, name in enumerate(chunk):
+            for q, sequence in enumerate(per_body[name]):
+                results[sequence] = opt_average_result(per_sequence[s][q])
+                frames_of_body[name] += per_sequence[s][q]
+                if report is not None:
+                    report(sequence, results[sequence])
+    final = {name: opt_average_result(frames_of_body[name]) for name in names}
+    final["all"] = opt_average_result([r for name in names for r in frames_of_body[name]])
+    return results, final

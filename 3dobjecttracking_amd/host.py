@@ -100,6 +100,16 @@ class Tracker:
         """the evaluators' judgement of `bodies` on the device (HIP library only): see Judge"""
         return Judge(self.api, bodies, n_rows_max)
 
+    def VerticesDiameter(self, vertices):
+        """OPTEvaluator::CalculateDiameters (opt_evaluator.cpp:580-600) of one vertex set on the device (HIP library
+        only): the largest distance between two vertices, as np.float32"""
+        if "vertices_diameter" not in self.api._fn:
+            raise M3TError(-3, "%svertices_diameter: this entry point exists in the HIP library only" % self.api.prefix)
+        v = np.ascontiguousarray(vertices, np.float32).reshape(-1, 3)
+        out = C.c_float(0.0)
+        self.api.call("vertices_diameter", fptr(v), len(v), C.byref(out))
+        return np.float32(out.value)
+
     # asynchronous ingest (HIP library only)
     def register_host_buffer(self, array):
         """page-lock a caller-owned frame buffer so that asynchronous uploads overlap the tracking kernels"""
@@ -151,6 +161,14 @@ class Judge:
         index = body if isinstance(body, (int, np.integer)) else [b.id for b in self.bodies].index(body.id)
         v = np.ascontiguousarray(vertices, np.float32).reshape(-1, 3)
         self.api.call("judge_set_vertices", self.id, int(index), fptr(v), len(v))
+
+    def set_add_only(self, body, geometry2body=None):
+        """judge `body` (a listed Body or its index in the list) as OPTEvaluator::CalculatePoseResults does
+        (opt_evaluator.cpp:462-488): ADD over its evaluation vertices with `geometry2body` (4x4, None: identity) on both
+        sides of the pose difference, no nearest-vertex search (adds_error = 0)"""
+        index = body if isinstance(body, (int, np.integer)) else [b.id for b in self.bodies].index(body.id)
+        g = None if geometry2body is None else fptr(pose_arg(geometry2body))
+        self.api.call("judge_set_add_only", self.id, int(index), g)
 
     def raw_judge(self, gt_poses, reset_iteration=-1):
         """(status, row) without raising"""

@@ -392,7 +392,22 @@ int m3t_hip_reset_structures(m3t_hip_context*, const int* optimizer_ids, int n, 
  * the stream and uploads (outside the frame loop); M3T_ERR_INVALID_ARGUMENT: a bad judge, lists that are not ascending
  * from 0, an empty structure or group, an index outside the judge's list, a body of a group without evaluation
  * vertices, rows already judged (judge_clear first).  judge_read_structures is judge_read for these rows:
- * out[n_rows][n_structures]. */
+ * out[n_rows][n_structures].
+ * ADD-only bodies (OPTEvaluator::CalculatePoseResults, examples/opt_evaluator.cpp:462-488).  judge_set_add_only marks
+ * listed body `index`; geometry2body_pose is the body's geometry-to-body pose (16 floats, column-major, bottom row
+ * (0, 0, 0, 1); NULL: identity).  From then on judge_bodies judges that body by kernels of its own:
+ *   delta = (body2world * geometry2body)^-1 * gt * geometry2body (:466-468) in f64, left to right, every sum left to
+ *   right as the existing delta's: a = body2world * geometry2body (3 x 4, the bottom rows implied), its rigid inverse
+ *   [R^T | -R^T t], that times gt exactly as the existing delta is formed, the result times geometry2body, rounded to
+ *   f32 once.  With the identity the extra products add exact zeros: delta has the bits of the existing one.
+ *   add_error = the mean of |v - delta v| over the body's evaluation vertices (judge_set_vertices; none: 0), the
+ *   per-vertex arithmetic in f32 as for every other body, sums in f64 in a fixed order; adds_error = 0, the
+ *   nearest-vertex search is not run for this body.
+ * Pose errors, tracking_success, was_reset and the reset with its refusals are as for every other body; bodies not
+ * marked keep their judgement and its bits, and a judge may mix both kinds.  Curve and area under curve stay with the
+ * host (three f32 operations from add_error).  The call waits for the stream and uploads (outside the frame loop);
+ * M3T_ERR_INVALID_ARGUMENT: a bad judge or index, rows already judged (judge_clear first), a non-finite entry of the
+ * pose. */
 int m3t_hip_judge_create(m3t_hip_context*, const int* body_ids, int n_bodies, int n_rows_max, int* judge);
 int m3t_hip_judge_set_thresholds(m3t_hip_context*, int judge, float translation_error_threshold,
                                  float rotation_error_threshold);
@@ -406,6 +421,18 @@ int m3t_hip_judge_set_structures(m3t_hip_context*, int judge, int n_structures,
                                  const float* error_thresholds /* n_structures */);
 int m3t_hip_judge_read_structures(m3t_hip_context*, int judge, int first_row, int n_rows,
                                   m3t_structure_judgement* out /* [n_rows][n_structures] */);
+int m3t_hip_judge_set_add_only(m3t_hip_context*, int judge, int index,
+                               const float* geometry2body_pose /* 16, column-major, or NULL: identity */);
+/* OPTEvaluator::CalculateDiameters (examples/opt_evaluator.cpp:580-600): the largest distance between two of n_vertices
+ * vertices (xyz, 3 floats each), by exhaustive search on the device.  For every pair, in f32, every operation rounded,
+ * no contraction: dx = xi - xj, dy, dz likewise, d2 = (dx*dx + dy*dy) + dz*dz -- the order of the judge's other norms --
+ * and *diameter = sqrtf(max d2).  sqrtf is correctly rounded and monotone, so this is the maximum of the per-pair
+ * norms; d2(i, j) == d2(j, i) exactly, so half the pairs are formed; a maximum does not depend on the order it is taken
+ * in, so the result is one bit pattern whatever the tiling.  n_vertices == 1 gives 0.  The call waits for the stream,
+ * uploads and waits for its result (outside the frame loop) and leaves the tracking state untouched.
+ * M3T_ERR_INVALID_ARGUMENT, *diameter unchanged: n_vertices outside [1, 1 << 20] (checked before anything is read), a
+ * null pointer, a non-finite coordinate (checked on the host before anything is uploaded). */
+int m3t_hip_vertices_diameter(m3t_hip_context*, const float* xyz, int n_vertices, float* diameter);
 int m3t_hip_calculate_correspondences(m3t_hip_context*, int iteration, int corr_iteration); /* :447 */
 int m3t_hip_calculate_gradient_and_hessian(m3t_hip_context*, int iteration, int corr_iteration,
                                            int opt_iteration);                    /* :471 */

@@ -487,6 +487,11 @@ class Tracker {
                                            int(vertices.size())),
                 "Judge");
     }
+    // OPTEvaluator::CalculatePoseResults (opt_evaluator.cpp:462-488) for listed body `index` from now on: ADD alone,
+    // geometry2body on both sides of the pose difference (nullptr: identity)
+    void SetAddOnly(int index, const Pose* geometry2body = nullptr) {
+      c_->Check(m3t_hip_judge_set_add_only(c_->get(), id_, index, geometry2body ? geometry2body->data() : nullptr), "Judge");
+    }
     int JudgeBodies(const std::vector<Pose>& gt_body2world_poses, int reset_iteration = -1) {
       int row = -1;
       if (gt_body2world_poses.size() != n_) return -1;
@@ -528,6 +533,13 @@ class Tracker {
     int id_ = -1;
   };
   Judge CreateJudge(const std::vector<const Body*>& bodies, int n_rows_max) { return Judge(c_, bodies, n_rows_max); }
+  // OPTEvaluator::CalculateDiameters (opt_evaluator.cpp:580-600): the largest distance between two of the vertices
+  float VerticesDiameter(const std::vector<std::array<float, 3>>& vertices) const {
+    float diameter = 0.0f;
+    c_->Check(m3t_hip_vertices_diameter(c_->get(), vertices.empty() ? nullptr : vertices[0].data(), int(vertices.size()),
+                                        &diameter), "Tracker");
+    return diameter;
+  }
 
   // ---- the batch at once, and what has no counterpart in the reference (m3t_hip.h) ----
   // poses of the first n bodies in creation order, one copy each way
