@@ -23,6 +23,7 @@
 #include "../../include/m3t_hip.h"
 #include "m3t_device.h"
 #include "m3t_view_rows.h"
+#include "m3t_step_plan.h"
 #include "m3t_kernels.hip"
 #include "m3t_judge.hip"
 #include "m3t_opt.hip"
@@ -32,6 +33,11 @@
 #include "m3t_links.hip"
 #include "m3t_structures.hip"
 #include "m3t_ingest.hip"
+
+static_assert(m3t_step::kBlockThreads == M3T_BLOCK_THREADS && m3t_step::kCompactThreads == M3T_COMPACT_THREADS &&
+                  m3t_step::kSplitLanes == M3T_SPLIT_LANES && m3t_step::kSplitMaxParts == M3T_SPLIT_MAX_PARTS &&
+                  m3t_step::kMiscBytes == M3T_MISC_FLOATS * 4,
+              "m3t_step_plan.h and m3t_device.h disagree");
 
 namespace {
 
@@ -313,8 +319,9 @@ struct m3t_hip_context {
   unsigned* table_overflow_dev = nullptr;
   bool compact_possible = false;       // every modality fits the kernel's assumptions (UploadTables)
   bool compact_fuses_histogram = false;  // ... and the count table fits next to the scratch block (<= 16 bins)
-  const char* last_step_kernel = "";   // m3t_hip_get_step_kernel
-  bool last_step_moments_first = false;  // m3t_hip_get_step_variant: the split kernel's moments-first instantiation
+  // what the last step launched (m3t_step_plan.h): m3t_hip_get_step_variant reports it, m3t_hip_get_step_kernel too
+  // except that the split kernel's moments-first instantiation goes by the split kernel's name there
+  m3t_step::StepKernel last_step_kernel = m3t_step::StepKernel::kNone;
   // ROI ingest (m3t_ingest.hip): rectangles instead of whole frames
   bool roi_enabled = false;        // m3t_hip_set_roi_ingest
   bool roi_adaptive = false;       // ... with enable = 2: per-body margins from the motion over the last step
@@ -646,6 +653,19 @@ int ResidentBlocks(Ctx* ctx, K kernel, int threads, size_t lds) {
   return resident;
 }
 
+// A word the kernels write with system scope and the host reads in place: 64 zeroed bytes of mapped host memory,
+// allocated on first use and freed in m3t_hip_destroy.
+int MappedWord(Ctx* ctx, unsigned** host, unsigned** dev) {
+  if (*host) return M3T_OK;
+  void *h = nullptr, *d = nullptr;
+  HIPCHK(hipHostMalloc(&h, 64, hipHostMallocMapped));
+  std::memset(h, 0, 64);
+  HIPCHK(hipHostGetDevicePointer(&d, h, 0));
+  *host = static_cast<unsigned*>(h);
+  *dev = static_cast<unsigned*>(d);
+  return M3T_OK;
+}
+
 // After a synchronisation: did the workgroups of a split object ever give up waiting for each other?  (They
 // are all resident by construction; the bounded wait exists so that a surprise cannot hang the device.)
 int CheckSplitExchange(Ctx* ctx) {
@@ -654,10 +674,11 @@ int CheckSplitExchange(Ctx* ctx) {
   const unsigned value = __atomic_load_n(ctx->split_abort_host, __ATOMIC_ACQUIRE);
   if (value != ctx->split_abort_seen) {
     ctx->split_abort_seen = value;
-    const bool tree = std::strncmp(ctx->last_step_kernel, "tracking_step_tree_", 19) == 0;
-    const bool render = std::strcmp(ctx->last_step_kernel, "tracking_step_split_render_kernel") == 0;
+    using m3t_step::StepKernel;
+    const bool tree = m3t_step::IsTreeStepKernel(ctx->last_step_kernel);
+    const bool render = ctx->last_step_kernel == StepKernel::kSplitRender;
     const std::string msg =
-        std::string(tree ? ctx->last_step_kernel : (render ? "tracking_step_split_render_kernel" : "tracking_step_split_kernel")) +
+        std::string(m3t_step::StepKernelName(tree || render ? ctx->last_step_kernel : StepKernel::kSplit)) +
         ": a workgroup waited in vain for the other workgroups of its " + (tree ? "kinematic structure" : "object") +
         " (is another process or stream using this GPU?); the step was abandoned part-way: workgroups that had "
         "already finished may have written the new pose" + (tree ? "s and joints" : "") +
@@ -1820,11 +1841,11 @@ size_t TreeStepLds(Ctx* ctx, bool fused_histogram) {
 // links (at most one region and one depth modality per link), no renderer-fed branches, no communicator, no shared
 // histogram objects, line / point state not requested (fused mode 1), fewer than 63 Newton steps per frame, the
 // structure copy next to the tracking carve-up in LDS, and every workgroup of the grid resident at once.
-bool TreeStepFused(Ctx* ctx) {
+bool TreeStepFused(Ctx* ctx, const m3t_step::StepOverrides& overrides) {
   // (m3t_hip_set_object_split(ctx, 0) = "this context shares its GPU": no launch whose workgroups wait for each other)
   if (!(ctx->tree_mode && ctx->tree_fused_possible && ctx->fused_mode == 1 && !ctx->Distributed() && ctx->n_render_all == 0 &&
         ctx->shared_histograms.empty() && ctx->n_treesteps > 0 && ctx->split_enabled &&
-        !std::getenv("M3T_HIP_NO_TREE_FUSION")))
+        !overrides.no_tree_fusion))
     return false;
   if (ctx->layout.off_hist >= 0) return false;  // (the LDS-staged pair table belongs to tracking_step_lds_kernel)
   if (ctx->n_corr_iterations * ctx->n_update_iterations >= 63) return false;
@@ -1849,9 +1870,9 @@ bool TreeStepFused(Ctx* ctx) {
 // A structure spread over processes (a communicator is set): can the step run as ONE launch + ONE all-reduce per
 // Newton step (tracking_step_tree_segment_kernel)?  The conditions of the one-launch step, except that no workgroup
 // waits for another one inside a launch: no co-residency needed, any grid.
-bool TreeStepSegmented(Ctx* ctx) {
+bool TreeStepSegmented(Ctx* ctx, const m3t_step::StepOverrides& overrides) {
   if (!(ctx->tree_mode && ctx->tree_fused_possible && ctx->fused_mode == 1 && ctx->Distributed() && ctx->n_render_all == 0 &&
-        ctx->shared_histograms.empty() && ctx->n_treesteps > 0 && !std::getenv("M3T_HIP_NO_TREE_SEGMENTS")))
+        ctx->shared_histograms.empty() && ctx->n_treesteps > 0 && !overrides.no_tree_segments))
     return false;
   // a structure's solve is done by the workgroups of its tracked links: one whose modalities all live on other ranks
   // has none here, and still has to be solved from the summed link sums -> the per-sub-step launches (grid = structures)
@@ -4588,54 +4609,104 @@ int m3t_hip_calculate_results(m3t_hip_context* ctx, int iteration) {
   return LaunchHistogram(ctx, iteration, false);
 }
 
-// tracking_step_split_kernel / _split_render_kernel: how many workgroups per object (0: none) for a batch of n.
-// parts x padded elements per part = 256 (the collecting threads of split_exchange_state); the grid must fit the GPU
-// with every workgroup resident at once (their in-kernel exchange needs that).
-extern "C++" {
-template <typename K>
-static int ChooseSplitParts(Ctx* ctx, K kernel, int n, int threads, bool want_fused_histogram, size_t* lds_out,
-                     int default_limit = 8) {
-  const size_t lds_tracking = size_t(ctx->layout.off_hist >= 0 ? ctx->layout.off_hist : ctx->layout.total_floats) * 4;
-  // (each workgroup counts its share of the histogram bins: that share of the count table; the pair table is
-  // read from L2, never staged)
-  auto lds_split_for = [&](int p) {
-    return want_fused_histogram ? std::max(lds_tracking, M3T_MISC_FLOATS * 4 + (ctx->lds_hist - M3T_MISC_FLOATS * 4) / p)
-                                : lds_tracking;
-  };
-  // (default_limit: 8 for the one-launch step -- 16 was not faster there in round 2; 16 for the per-search launches of
-  // renderer-fed steps, measured 0.643 -> 0.635 ms for one object)
-  int limit = ctx->split_parts_override > 1 ? ctx->split_parts_override : default_limit;
-  if (const char* e = std::getenv("M3T_HIP_SPLIT_PARTS")) limit = std::atoi(e);  // developer override
-  const int elements = std::max(ctx->layout.nl, ctx->depth_mods.empty() ? 1 : ctx->np_max);
-  for (int p = M3T_SPLIT_MAX_PARTS; p >= 2; p >>= 1) {
-    // 256-thread workgroups (developer override): two are resident per CU if their LDS fits twice
-    const int per_cu = (threads == M3T_SPLIT_LANES && lds_split_for(p) * 2 <= size_t(160) * 1024) ? 2 : 1;
-    const int padded = (n + 7) / 8 * 8;  // grid blocks / p: every XCD gets the blocks of the fullest one
-    if (p > limit || padded * p > ctx->compute_cus * per_cu) continue;
-    if ((elements + p - 1) / p > M3T_SPLIT_LANES / p) continue;  // a part's elements fit its share of the lanes
-    // the exchange needs every workgroup of the grid resident at once: ask the runtime how many of these
-    // workgroups (registers, LDS) a CU takes, instead of assuming the LDS arithmetic above is the only limit
-    int resident = ResidentBlocks(ctx, kernel, threads, lds_split_for(p));
-    if (resident > per_cu) resident = per_cu;  // (the query is known to over-report by one block for SGPR-heavy kernels)
-    if (resident < 1 || padded * p > ctx->compute_cus * resident) continue;
-    *lds_out = lds_split_for(p);
-    return p;
+}  // extern "C"
+namespace {
+// ---- the tracking step: its launch choice is m3t_step_plan.h, one function per path below ---------------------------
+using m3t_step::StepKernel;
+using m3t_step::StepOverrides;
+
+// What a path launched; m3t_hip_execute_tracking_step stores it into the context.
+struct StepReport {
+  StepKernel kernel = StepKernel::kNone;
+  int shape[4] = {0, 0, 0, 0};  // objects or tracked links, workgroups per each, threads, histogram update in the launch
+  bool histogram_fused = false;
+  bool state_valid = false;         // line/point state + g/H on the device reflect the step
+  bool links_device_newer = false;  // the step wrote the joints
+  void Launched(StepKernel k, int n, int parts, int threads, bool fused_histogram) {
+    kernel = k;
+    shape[0] = n, shape[1] = parts, shape[2] = threads, shape[3] = fused_histogram ? 1 : 0;
+    histogram_fused = fused_histogram;
   }
-  return 0;
+};
+
+// ResidentBlocks of the kernels whose workgroups wait for each other (the plan asks by name)
+int ResidentStepBlocks(Ctx* ctx, StepKernel kernel, int threads, size_t lds) {
+  switch (kernel) {
+    case StepKernel::kSplit: return ResidentBlocks(ctx, tracking_step_split_kernel, threads, lds);
+    case StepKernel::kSplitPair: return ResidentBlocks(ctx, tracking_step_split_pair_kernel, threads, lds);
+    case StepKernel::kSplitMoments: return ResidentBlocks(ctx, tracking_step_split_moments_kernel, threads, lds);
+    case StepKernel::kSplitGuard: return ResidentBlocks(ctx, tracking_step_split_guard_kernel, threads, lds);
+    case StepKernel::kSplitRender: return ResidentBlocks(ctx, tracking_step_split_render_kernel, threads, lds);
+    default: return 0;
+  }
 }
-}  // extern "C++"
+
+// what the plan reads of the context (the table-overflow word: StepRigidFused)
+m3t_step::RigidStepFacts RigidFacts(Ctx* ctx, bool roi_frames) {
+  m3t_step::RigidStepFacts f;
+  f.n = int(ctx->opt_table.size());
+  f.compute_cus = ctx->compute_cus;
+  f.lds_track = ctx->lds_track;
+  f.lds_hist = ctx->lds_hist;
+  f.lds_compact = ctx->lds_compact;
+  f.lds_compact_table = ctx->lds_compact_table;
+  f.table_cap = ctx->compact_table.table_cap;
+  f.off_hist = ctx->layout.off_hist;
+  f.total_floats = ctx->layout.total_floats;
+  f.nl = ctx->layout.nl;
+  f.np_max = ctx->np_max;
+  f.has_region = !ctx->region_mods.empty();
+  f.has_depth = !ctx->depth_mods.empty();
+  f.regions_allow_moments_first = true;
+  for (auto& m : ctx->region_mods)
+    f.regions_allow_moments_first = f.regions_allow_moments_first &&
+                                    m3t_step::RegionAllowsMomentsFirst(m->dev.measure_occlusions, m->dev.model_occlusions,
+                                                                       m->dev.use_region_checking, m->dev.n_global_iterations);
+  f.n_corr_iterations = ctx->n_corr_iterations;
+  f.n_update_iterations = ctx->n_update_iterations;
+  f.fused_mode = ctx->fused_mode;
+  f.fuse_histogram_possible = ctx->fuse_histogram_possible;
+  f.split_possible = ctx->split_possible;
+  f.split_enabled = ctx->split_enabled;
+  f.split_parts_override = ctx->split_parts_override;
+  f.compact_possible = ctx->compact_possible;
+  f.compact_fuses_histogram = ctx->compact_fuses_histogram;
+  f.roi_frames = roi_frames;
+  return f;
+}
+
+// The launches.  The step kernels of rigid objects share their first 13 arguments, the compact ones 10, the kinematic
+// structures' 11; what follows (SplitParams, RoiGuardArgs, the first search of a per-search launch, ...) is the caller's.
+template <typename K, typename... Tail>
+void LaunchRigid(Ctx* ctx, K kernel, int grid, int threads, size_t lds, int iteration, int n_corr_iterations,
+                 bool histogram_fused, Tail... tail) {
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(threads), lds, ctx->stream, ctx->d_opts.as<RigidOptDev>(),
+                     ctx->d_region.as<RegionModDev>(), ctx->d_depth.as<DepthModDev>(), ctx->cams_active,
+                     ctx->d_poses.as<float>(), ctx->layout, ctx->off_points, ctx->np_max, iteration, n_corr_iterations,
+                     ctx->n_update_iterations, ctx->fused_mode == 2 ? 1 : 0, histogram_fused ? 1 : 0, tail...);
+}
+template <typename K, typename... Tail>
+void LaunchCompact(Ctx* ctx, K kernel, int grid, int threads, size_t lds, const CompactLayout& layout, int iteration,
+                   bool histogram_fused, Tail... tail) {
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(threads), lds, ctx->stream, ctx->d_opts.as<RigidOptDev>(),
+                     ctx->d_region.as<RegionModDev>(), ctx->d_depth.as<DepthModDev>(), ctx->cams_active,
+                     ctx->d_poses.as<float>(), layout, iteration, ctx->n_corr_iterations, ctx->n_update_iterations,
+                     histogram_fused ? 1 : 0, tail...);
+}
+template <typename K, typename... Tail>
+void LaunchTree(Ctx* ctx, K kernel, int grid, size_t lds, int iteration, Tail... tail) {
+  const int off_tree = int((lds / 4 - ctx->tree_block_floats));
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(M3T_BLOCK_THREADS), lds, ctx->stream, ctx->d_treesteps.as<TreeStepDev>(),
+                     ctx->d_treeopts.as<TreeOptDev>(), ctx->d_region.as<RegionModDev>(), ctx->d_depth.as<DepthModDev>(),
+                     ctx->cams_active, ctx->d_poses.as<float>(), ctx->layout, ctx->off_points, ctx->np_max, off_tree,
+                     iteration, tail...);
+}
+
 // the exchange buffers and the per-launch descriptor of a split launch
-static int PrepareSplit(Ctx* ctx, int n, int parts, SplitParams* out) {
+int PrepareSplit(Ctx* ctx, int n, int parts, SplitParams* out) {
   const size_t per_object = size_t(2) * M3T_SPLIT_LANES * 32;  // granules
-  if (!ctx->split_abort_host) {
-    void* host = nullptr;
-    HIPCHK(hipHostMalloc(&host, 64, hipHostMallocMapped));
-    std::memset(host, 0, 64);
-    void* dev = nullptr;
-    HIPCHK(hipHostGetDevicePointer(&dev, host, 0));
-    ctx->split_abort_host = static_cast<unsigned*>(host);
-    ctx->split_abort_dev = static_cast<unsigned*>(dev);
-  }
+  int r = MappedWord(ctx, &ctx->split_abort_host, &ctx->split_abort_dev);
+  if (r) return r;
   if (ctx->split_objects < size_t(n) || ctx->split_seq >= (1u << 26) - 1) {
     HIPCHK(hipStreamSynchronize(ctx->stream));
     if (ctx->split_objects < size_t(n)) {
@@ -4663,17 +4734,310 @@ static int PrepareSplit(Ctx* ctx, int n, int parts, SplitParams* out) {
   return M3T_OK;
 }
 
+// Rigid objects, the whole loop nest in one launch (m3t_step_plan.h: PlanRigidStep says which).
+int StepRigidFused(Ctx* ctx, int iteration, const StepOverrides& overrides, bool roi_frames, StepReport* report) {
+  const int n = int(ctx->opt_table.size());
+  ScopedKernelTimer timer(ctx, 0);
+  m3t_step::RigidStepFacts facts = RigidFacts(ctx, roi_frames);
+  if (ctx->table_overflow_host) facts.table_overflow = *static_cast<volatile unsigned*>(ctx->table_overflow_host);
+  const m3t_step::RigidStepPlan plan = m3t_step::PlanRigidStep(
+      facts, overrides, [ctx](StepKernel k, int threads, size_t lds) { return ResidentStepBlocks(ctx, k, threads, lds); });
+  int r = M3T_OK;
+  if (plan.compact_table) {
+    if ((r = MappedWord(ctx, &ctx->table_overflow_host, &ctx->table_overflow_dev))) return r;
+    ctx->compact_table.table_overflow = ctx->table_overflow_dev;
+  }
+  report->kernel = plan.kernel;
+  // a step that reads rectangles runs the guarded kernels (m3t_kernels.hip, roi_guard_outside): an object whose poses
+  // leave what was uploaded is not committed but flagged; roi_repair_kernel then fetches the whole frames of the
+  // flagged objects' cameras and the step is launched again for the flagged objects alone
+  RoiGuardArgs guard{};
+  if (roi_frames) {
+    guard.items = ctx->d_roi_items.as<RoiItemDev>();
+    guard.rects = ctx->d_roi_rects.as<m3t_roi_rect>();
+    guard.n_cams = int(ctx->cameras.size());
+    guard.n_rect_slots = ctx->roi_rect_slots;
+    guard.n_poses = ctx->roi_n_poses;
+    guard.mode = 1;
+    guard.misses = ctx->roi_miss_dev;
+    guard.miss_capacity = int(Ctx::kRoiMissCapacity);
+    guard.unrecovered = ctx->roi_unrecovered_dev;
+  }
+  const int grid = plan.grid(n), threads = plan.threads, n_corr = ctx->n_corr_iterations;
+  const size_t lds = plan.lds;
+  const bool fused = plan.histogram_fused;
+  // pass 0: the step; passes 1 (repair) and 2 (the flagged objects again, on whole frames) only behind rectangles
+  for (int pass = 0; pass < (roi_frames ? 2 : 1); ++pass) {
+    if (pass == 1) {
+      for (size_t sl = 0; sl < ctx->roi_sources.size(); ++sl)
+        for (const Ctx::RoiSource& source : ctx->roi_sources[sl]) {
+          const Camera& c0 = *ctx->cameras[source.ids[0]];
+          if (c0.current != int(sl) || !c0.slot_is_roi[sl]) continue;  // (this step reads another slot of these cameras)
+          m3t_roi_rect* rects = ctx->d_roi_rects.as<m3t_roi_rect>() + sl * ctx->cameras.size();
+          hipLaunchKernelGGL(roi_repair_kernel, dim3((c0.intr.height + 7) / 8, unsigned(source.ids.size())), dim3(256), 0,
+                             ctx->stream, source.d_ids, ctx->d_roi_items.as<RoiItemDev>(), ctx->d_roi_item_first.as<int>(),
+                             ctx->d_opts.as<RigidOptDev>(), ctx->roi_n_poses, rects, source.src, source.camera_stride,
+                             source.row_step, c0.frame(int(sl)), c0.frame_bytes, c0.pitch, c0.intr.width, c0.intr.height,
+                             c0.is_depth ? 2 : 3);
+        }
+      guard.mode = 2;
+    }
+    SplitParams sp{};
+    if (plan.split() && (r = PrepareSplit(ctx, n, plan.parts, &sp))) return r;
+    switch (plan.kernel) {
+      case StepKernel::kCompactGuard:
+        LaunchCompact(ctx, tracking_step_compact_guard_kernel, grid, threads, lds, ctx->compact, iteration, fused, guard);
+        break;
+      case StepKernel::kCompactTable:
+        LaunchCompact(ctx, tracking_step_compact_table_kernel, grid, threads, lds, ctx->compact_table, iteration, fused);
+        break;
+      case StepKernel::kCompactWide:
+        LaunchCompact(ctx, tracking_step_compact_wide_kernel, grid, threads, lds, ctx->compact, iteration, fused);
+        break;
+      case StepKernel::kCompact:
+        LaunchCompact(ctx, tracking_step_compact_kernel, grid, threads, lds, ctx->compact, iteration, fused);
+        break;
+      case StepKernel::kSplitGuard:
+        LaunchRigid(ctx, tracking_step_split_guard_kernel, grid, threads, lds, iteration, n_corr, fused, sp, guard);
+        break;
+      case StepKernel::kSplitPair:
+        LaunchRigid(ctx, tracking_step_split_pair_kernel, grid, threads, lds, iteration, n_corr, fused, sp);
+        break;
+      case StepKernel::kSplitMoments:
+        LaunchRigid(ctx, tracking_step_split_moments_kernel, grid, threads, lds, iteration, n_corr, fused, sp);
+        break;
+      case StepKernel::kSplit:
+        LaunchRigid(ctx, tracking_step_split_kernel, grid, threads, lds, iteration, n_corr, fused, sp);
+        break;
+      case StepKernel::kLdsGuard:
+        LaunchRigid(ctx, tracking_step_lds_guard_kernel, grid, threads, lds, iteration, n_corr, fused, guard);
+        break;
+      case StepKernel::kGuard:
+        LaunchRigid(ctx, tracking_step_guard_kernel, grid, threads, lds, iteration, n_corr, fused, guard);
+        break;
+      case StepKernel::kLdsPair:
+        LaunchRigid(ctx, tracking_step_lds_pair_kernel, grid, threads, lds, iteration, n_corr, fused, 0);
+        break;
+      case StepKernel::kPair:
+        LaunchRigid(ctx, tracking_step_pair_kernel, grid, threads, lds, iteration, n_corr, fused, 0);
+        break;
+      case StepKernel::kLds:
+        LaunchRigid(ctx, tracking_step_lds_kernel, grid, threads, lds, iteration, n_corr, fused, 0);
+        break;
+      case StepKernel::kPlain:
+        LaunchRigid(ctx, tracking_step_kernel, grid, threads, lds, iteration, n_corr, fused, 0);
+        break;
+      default:
+        return Fail(ctx, M3T_ERR_DEVICE, std::string("no launch for the planned kernel ") + m3t_step::StepKernelName(plan.kernel));
+    }
+    HIPCHK(hipGetLastError());
+  }
+  // (where the repair fetched a whole frame only the device's rectangle table knows it: for the host the slot keeps
+  // counting as a rectangle slot -- conservative -- until the next upload into it)
+  report->Launched(plan.kernel, n, plan.split() ? plan.parts : 1, threads, fused);
+  report->state_valid = ctx->fused_mode == 2;
+  return M3T_OK;
+}
+
+// Renderer-fed branches (modelled occlusions, region / silhouette checking): the focused renderings are redrawn
+// before every correspondence search from the bodies' current poses (correspondence_renderer_ptrs,
+// tracker.cpp:447-452), so the loop nest runs one search per launch -- the renderers, then ONE launch for the
+// search and its Newton steps of all objects -- instead of one launch per sub-step: 4 instead of 11 per search.
+int StepPerSearch(Ctx* ctx, int iteration, const StepOverrides& overrides, StepReport* report) {
+  ScopedKernelTimer timer(ctx, 0);
+  const int n = int(ctx->opt_table.size());
+  // a batch that leaves CUs idle: several workgroups per object here too (tracking_step_split_render_kernel: the
+  // split kernel with the renderer-fed branches compiled in, one search per launch)
+  int parts = 0, r = M3T_OK;
+  size_t lds_split = 0;
+  bool shared = false;
+  for (auto& m : ctx->region_mods) shared = shared || m->shared_histograms >= 0 || m->p.n_histogram_bins < 4;
+  if (!shared && ctx->split_enabled && ctx->n_corr_iterations < 64 && !overrides.no_split)
+    parts = m3t_step::RigidSplitParts(
+        RigidFacts(ctx, false), overrides, StepKernel::kSplitRender, M3T_BLOCK_THREADS, false, 16,
+        [ctx](StepKernel k, int threads, size_t lds) { return ResidentStepBlocks(ctx, k, threads, lds); }, &lds_split);
+  const bool lds_table = ctx->layout.off_hist >= 0;
+  for (int c = 0; c < ctx->n_corr_iterations; ++c) {
+    if ((r = RenderForModalities(ctx, false))) return r;
+    if (parts >= 2) {
+      SplitParams sp{};
+      if ((r = PrepareSplit(ctx, n, parts, &sp))) return r;
+      hipLaunchKernelGGL(tracking_step_split_render_kernel, dim3((n + 7) / 8 * 8 * parts), dim3(M3T_BLOCK_THREADS),
+                         lds_split, ctx->stream, ctx->d_opts.as<RigidOptDev>(), ctx->d_region.as<RegionModDev>(),
+                         ctx->d_depth.as<DepthModDev>(), ctx->cams_active, ctx->d_poses.as<float>(), ctx->layout,
+                         ctx->off_points, ctx->np_max, iteration, ctx->n_update_iterations,
+                         ctx->fused_mode == 2 ? 1 : 0, c, sp);
+    } else if (lds_table) {
+      LaunchRigid(ctx, tracking_step_lds_kernel, n, M3T_BLOCK_THREADS, ctx->lds_track, iteration, 1, false, c);
+    } else {
+      LaunchRigid(ctx, tracking_step_kernel, n, M3T_BLOCK_THREADS, ctx->lds_track, iteration, 1, false, c);
+    }
+  }
+  HIPCHK(hipGetLastError());
+  report->Launched(parts >= 2 ? StepKernel::kSplitRender : (lds_table ? StepKernel::kLds : StepKernel::kPlain), n,
+                   parts >= 2 ? parts : 1, M3T_BLOCK_THREADS, false);
+  report->state_valid = ctx->fused_mode == 2;
+  return M3T_OK;
+}
+
+// kinematic structures: the whole loop nest in one launch, one workgroup per link that carries modalities
+int StepTreeFused(Ctx* ctx, int iteration, const StepOverrides& overrides, StepReport* report) {
+  ScopedKernelTimer timer(ctx, 0);
+  const bool want_fused_histogram = !ctx->region_mods.empty() && ctx->hist_counts_in_lds && ctx->shared_histograms.empty() &&
+                                    !overrides.no_fused_histogram;
+  const size_t lds = TreeStepLds(ctx, want_fused_histogram);
+  int r = MappedWord(ctx, &ctx->split_abort_host, &ctx->split_abort_dev);
+  if (r) return r;
+  if (ctx->tree_seq >= (1u << 26) - 1) {  // the tags restart: clear them first
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    HIPCHK(hipMemset(ctx->d_tree_exchange.p, 0, ctx->d_tree_exchange.bytes));
+    ctx->tree_seq = 0;
+  }
+  TreeStepParams xp{};
+  xp.seq = ++ctx->tree_seq;
+  if (++ctx->split_launches == 0) ctx->split_launches = 1;
+  xp.abort_id = ctx->split_launches;
+  xp.host_abort = ctx->split_abort_dev;
+  // Structures that leave CUs idle (the 8-body chain: 8 workgroups on 256 CUs): several workgroups per tracked link
+  // (tracking_step_tree_split_kernel; open structures only -- the constrained kernel keeps one).  The parts of a link
+  // exchange their lines' results, so all workgroups must be resident: checked like the split kernel's launch.
+  int tree_parts = 0;
+  if (!ctx->tree_constrained && ctx->n_corr_iterations < 64 && !overrides.no_tree_split) {
+    bool can = true;
+    for (auto& m : ctx->region_mods) can = can && m->shared_histograms < 0 && m->p.n_histogram_bins >= 4;
+    const int elements = std::max(ctx->layout.nl, ctx->depth_mods.empty() ? 1 : ctx->np_max);
+    // (the 8-body chain, ms per step: 1 part 0.3046, 2: 0.2939, 4: 0.2756, 8: 0.2649; profiles/r05_chain8_parts.txt)
+    const int limit = overrides.tree_parts.set ? overrides.tree_parts.value : 8;
+    if (can)
+      tree_parts = m3t_step::SplitParts(ctx->n_treesteps, elements, limit, ctx->compute_cus, [ctx, lds](int) {
+        if (ctx->tree_split_lds_attribute != lds) {
+          if (hipFuncSetAttribute(reinterpret_cast<const void*>(tracking_step_tree_split_kernel),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, int(lds)) != hipSuccess) {
+            (void)hipGetLastError();
+            return -1;
+          }
+          ctx->tree_split_lds_attribute = lds;
+        }
+        const int resident = ResidentBlocks(ctx, tracking_step_tree_split_kernel, M3T_BLOCK_THREADS, lds);
+        return std::min(resident, int(size_t(160) * 1024 / lds));
+      });
+  }
+  const int fuse = want_fused_histogram ? 1 : 0, n_corr = ctx->n_corr_iterations, n_update = ctx->n_update_iterations;
+  StepKernel kernel = ctx->tree_constrained ? StepKernel::kTreeConstrained : StepKernel::kTree;
+  if (tree_parts >= 2) {
+    SplitParams sp{};
+    if ((r = PrepareSplit(ctx, ctx->n_treesteps, tree_parts, &sp))) return r;
+    kernel = StepKernel::kTreeSplit;
+    LaunchTree(ctx, tracking_step_tree_split_kernel, ctx->n_treesteps * tree_parts, lds, iteration, n_corr, n_update, fuse, xp, sp);
+  } else if (ctx->tree_constrained) {
+    LaunchTree(ctx, tracking_step_tree_constrained_kernel, ctx->n_treesteps, lds, iteration, n_corr, n_update, fuse, xp);
+  } else {
+    LaunchTree(ctx, tracking_step_tree_kernel, ctx->n_treesteps, lds, iteration, n_corr, n_update, fuse, xp);
+  }
+  HIPCHK(hipGetLastError());
+  report->Launched(kernel, ctx->n_treesteps, tree_parts >= 2 ? tree_parts : 1, M3T_BLOCK_THREADS, want_fused_histogram);
+  report->links_device_newer = true;
+  report->state_valid = false;
+  return M3T_OK;
+}
+
+// kinematic structures spread over processes: one launch and one all-reduce (of the link sums) per Newton step,
+// a last launch for the last solve, the bodies and the histogram update (m3t_links.hip, tree_segment_body)
+int StepTreeSegmented(Ctx* ctx, int iteration, const StepOverrides& overrides, StepReport* report) {
+  ScopedKernelTimer timer(ctx, 0);
+  const bool want_fused_histogram = !ctx->region_mods.empty() && ctx->hist_counts_in_lds && ctx->shared_histograms.empty() &&
+                                    !overrides.no_fused_histogram;
+  const size_t lds = TreeStepLds(ctx, want_fused_histogram);
+  float* sums[2] = {ctx->d_link_sums.as<float>(), ctx->d_link_sums_alt.as<float>()};
+  const int n_newton = ctx->n_corr_iterations * ctx->n_update_iterations;
+  // launch k reads the link table launch k - 1 wrote: the primary table at k <= 1 (launch 0 solves nothing and writes
+  // nothing), then alternately; launch k >= 1 writes the other one.  The last launch (k = n_newton) must leave the
+  // joints in the primary table, the one the rest of the library reads: an odd n_newton ends in the second one and
+  // is copied over.
+  // FIRST (the links take their bodies' poses) and FINAL (the bodies take their links') meet in one launch only when
+  // the frame has a single Newton step: a workgroup that starts late would then seed from poses a faster one has
+  // already written back, so that launch seeds from a snapshot taken in front of the loop
+  const float* first_poses = ctx->d_poses.as<float>();
+  if (n_newton == 1) {
+    if (ctx->d_poses_first.bytes < ctx->d_poses.bytes) HIPCHK(ctx->d_poses_first.alloc(ctx->d_poses.bytes));
+    HIPCHK(hipMemcpyAsync(ctx->d_poses_first.p, ctx->d_poses.p, ctx->body_poses.size() * 4, hipMemcpyDeviceToDevice,
+                          ctx->stream));
+    first_poses = ctx->d_poses_first.as<float>();
+  }
+  for (int k = 0; k <= n_newton; ++k) {
+    TreeSegmentParams sp{};
+    const int c = k / std::max(ctx->n_update_iterations, 1), u = k % std::max(ctx->n_update_iterations, 1);
+    const bool last = k == n_newton;
+    int flags = 0;
+    if (k <= 1) flags |= TSEG_FIRST;  // (nothing has written the bodies' link2world yet: launch 0 solves nothing)
+    if (k > 0) flags |= TSEG_SOLVE;
+    if (!last) {
+      flags |= TSEG_SUMS;
+      if (u == 0) flags |= TSEG_SEARCH | (ctx->n_update_iterations > 1 ? TSEG_STORE_STATE : 0);
+      else flags |= TSEG_LOAD_STATE;
+    } else {
+      flags |= TSEG_FINAL;
+    }
+    const bool read_alt = k >= 2 && (k % 2 == 0);
+    const bool write_alt = k >= 1 && (k % 2 == 1);
+    if (read_alt) flags |= TSEG_LINKS_FROM_ALT;
+    if (write_alt) flags |= TSEG_LINKS_TO_ALT;
+    sp.flags = flags;
+    sp.corr_iteration = last ? 0 : c;
+    sp.opt_iteration = last ? 0 : u;
+    sp.sums_in = sums[(k + 1) & 1];  // what launch k - 1 wrote and the all-reduce summed
+    sp.sums_out = sums[k & 1];
+    sp.first_poses = first_poses;
+    const int fuse = (last && want_fused_histogram) ? 1 : 0;
+    if (ctx->tree_constrained)
+      LaunchTree(ctx, tracking_step_tree_segment_constrained_kernel, ctx->n_treesteps, lds, iteration, fuse, sp);
+    else
+      LaunchTree(ctx, tracking_step_tree_segment_kernel, ctx->n_treesteps, lds, iteration, fuse, sp);
+    HIPCHK(hipGetLastError());
+    if (!last) {
+      ctx->partial_ready = true;
+      int r = AllReducePartial(ctx, sums[k & 1]);
+      if (r) return r;
+      ctx->partial_ready = false;
+    }
+  }
+  if (n_newton >= 1 && (n_newton % 2 == 1))  // the last launch wrote the second table
+    HIPCHK(hipMemcpyAsync(ctx->d_links.p, ctx->d_links_alt.p, ctx->d_links.bytes, hipMemcpyDeviceToDevice, ctx->stream));
+  report->Launched(ctx->tree_constrained ? StepKernel::kTreeSegmentConstrained : StepKernel::kTreeSegment, ctx->n_treesteps, 1,
+                   M3T_BLOCK_THREADS, want_fused_histogram);
+  report->links_device_newer = true;
+  report->state_valid = false;
+  return M3T_OK;
+}
+
+// Tracker::ExecuteTrackingStep tracker.cpp:344-364, one launch per sub-step
+int StepSubSteps(Ctx* ctx, int iteration, StepReport* report) {
+  report->kernel = StepKernel::kNone;
+  int r = M3T_OK;
+  for (int c = 0; c < ctx->n_corr_iterations; ++c) {
+    if ((r = RenderForModalities(ctx, false))) return r;
+    if ((r = LaunchCorrespondences(ctx, iteration, c))) return r;
+    for (int u = 0; u < ctx->n_update_iterations; ++u) {
+      if ((r = LaunchGradientHessian(ctx, c, u))) return r;
+      if ((r = LaunchOptimization(ctx))) return r;
+    }
+  }
+  report->state_valid = true;
+  return M3T_OK;
+}
+}  // namespace
+extern "C" {
+
 int m3t_hip_execute_tracking_step(m3t_hip_context* ctx, int iteration) {
   CHECK_CTX();
   HIPCHK(hipSetDevice(ctx->device));
+  const StepOverrides overrides = m3t_step::ReadStepOverrides();  // every step: tests change them between two steps
   const bool untracked_before = ctx->untracked_launches;
   const bool host_poses_before = ctx->poses_dirty_host;  // (Prepare uploads them)
   int r = Prepare(ctx, true);
   if (r) return r;
   ctx->untracked_launches = untracked_before;  // a whole step is tracked by its step_done event below
   if ((r = CheckSplitExchange(ctx))) return r;  // an earlier step that was abandoned on the device
-  bool histogram_fused = false;
-  ctx->last_step_moments_first = false;
   const bool rigid_fused = ctx->fused_mode >= 1 && ctx->fused_possible && !ctx->Distributed();
   bool roi_frames = false;  // does this step read a slot that holds a rectangle only
   for (auto& cam : ctx->cameras) roi_frames = roi_frames || cam->slot_is_roi[cam->current];
@@ -4701,400 +5065,27 @@ int m3t_hip_execute_tracking_step(m3t_hip_context* ctx, int iteration) {
   }
   ctx->roi_end_valid = false;
   ctx->roi_recorded = roi_active;
-  // a step that reads rectangles runs the guarded kernels (m3t_kernels.hip, roi_guard_outside): an object whose poses
-  // leave what was uploaded is not committed but flagged; roi_repair_kernel then fetches the whole frames of the
-  // flagged objects' cameras and the step is launched again for the flagged objects alone
-  RoiGuardArgs guard{};
-  if (roi_frames) {
-    guard.items = ctx->d_roi_items.as<RoiItemDev>();
-    guard.rects = ctx->d_roi_rects.as<m3t_roi_rect>();
-    guard.n_cams = int(ctx->cameras.size());
-    guard.n_rect_slots = ctx->roi_rect_slots;
-    guard.n_poses = ctx->roi_n_poses;
-    guard.mode = 1;
-    guard.misses = ctx->roi_miss_dev;
-    guard.miss_capacity = int(Ctx::kRoiMissCapacity);
-    guard.unrecovered = ctx->roi_unrecovered_dev;
-  }
-  if (rigid_fused) {  // (a communicator: the structures span GPUs)
-    int n = int(ctx->opt_table.size());
-    ScopedKernelTimer timer(ctx, 0);
-    // From two objects per CU on (and if two working sets fit the CU's LDS) the kernel runs with 256-thread
-    // workgroups, two per CU: one object's serial solve overlaps the other's parallel phases and no register is
-    // spilled (measured, pose-updates/s: 512 objects 1.11 M vs 0.87 M with 512 threads, 4096: 1.24 M vs 0.91 M;
-    // 128-VGPR variants of the 512-thread kernel reached 1.03 M / 1.11 M)
-    int threads = M3T_BLOCK_THREADS;
-    if (n >= 2 * ctx->compute_cus && ctx->lds_track * 2 <= 160 * 1024) threads = M3T_BLOCK_THREADS / 2;
-    if (const char* e = std::getenv("M3T_HIP_THREADS")) threads = std::atoi(e);  // developer override
-    // Batches with region AND depth modalities: the _pair_ kernels (m3t_kernels.hip, PAIR: the two modalities' products
-    // side by side, their sums on two waves).  M3T_HIP_NO_PAIR: developer override.
-    const bool pair = !roi_frames && !ctx->region_mods.empty() && !ctx->depth_mods.empty() && !std::getenv("M3T_HIP_NO_PAIR");
-    // Region-only batches whose first Newton step after a search reads no distribution row (n_global_iterations >= 1)
-    // and whose searches have no occlusion vote to defer: the split kernel with the moments-first exchange
-    // (m3t_kernels.hip, region_distribution_rows).  Every object of the launch must qualify; all others keep
-    // tracking_step_split_kernel.  M3T_HIP_NO_MOMENTS_FIRST: developer override.
-    bool moments_first = !roi_frames && !pair && ctx->depth_mods.empty() && !ctx->region_mods.empty() &&
-                         ctx->n_update_iterations >= 1 && !std::getenv("M3T_HIP_NO_MOMENTS_FIRST");
-    for (auto& m : ctx->region_mods)
-      if (m->dev.measure_occlusions || m->dev.model_occlusions || m->dev.use_region_checking || m->dev.n_global_iterations < 1)
-        moments_first = false;
-    auto split_kernel = pair ? tracking_step_split_pair_kernel
-                             : (moments_first ? tracking_step_split_moments_kernel : tracking_step_split_kernel);
-    auto kernel = pair ? (ctx->layout.off_hist >= 0 ? tracking_step_lds_pair_kernel : tracking_step_pair_kernel)
-                       : (ctx->layout.off_hist >= 0 ? tracking_step_lds_kernel : tracking_step_kernel);
-    // One workgroup per CU: the histogram update (CalculateResults) runs at the end of the same launch, its
-    // count table taking over the line buffers' LDS.  With two workgroups per CU that table (128 KB at 32 bins)
-    // would not fit twice, so large batches keep the separate region_histogram_kernel.
-    const bool want_fused_histogram = ctx->fuse_histogram_possible && !std::getenv("M3T_HIP_NO_FUSED_HISTOGRAM");
-    histogram_fused = want_fused_histogram && threads == M3T_BLOCK_THREADS;
-    const size_t lds = histogram_fused ? std::max(ctx->lds_track, ctx->lds_hist) : ctx->lds_track;
-    // Batches that leave CUs idle: several workgroups per object, each on its own CU (all resident at once, which
-    // their in-kernel exchange needs; a wait that runs out abandons the object's step, see CheckSplitExchange).
-    // parts x padded elements per part = 256 (the collecting threads of split_exchange_state).
-    int parts = 0;
-    size_t lds_split = 0;
-    if (ctx->split_possible && ctx->split_enabled && threads % M3T_SPLIT_LANES == 0 &&
-        ctx->n_corr_iterations < 64 && !std::getenv("M3T_HIP_NO_SPLIT"))
-      parts = roi_frames ? ChooseSplitParts(ctx, tracking_step_split_guard_kernel, n, threads, want_fused_histogram, &lds_split)
-                         : ChooseSplitParts(ctx, split_kernel, n, threads,
-                                            want_fused_histogram, &lds_split);
-    const bool split = parts >= 2;
-    ctx->last_step_moments_first = split && moments_first;
-    // More objects than CUs: the compact kernel (<= 47 KB of LDS, <= 128 VGPRs per object: 3-4 workgroups per CU;
-    // measured crossover on 256 CUs: 256 objects 0.249 vs 0.225 ms with one 512-thread workgroup per CU, 384 objects
-    // 0.309 vs 0.426 ms).  M3T_HIP_COMPACT=0 / 1: developer override (never / whenever possible).
-    bool compact = !split && ctx->compact_possible && ctx->fused_mode == 1 && n > ctx->compute_cus;
-    if (const char* e = std::getenv("M3T_HIP_COMPACT")) compact = !split && ctx->compact_possible && ctx->fused_mode == 1 && std::atoi(e) != 0;
-    if (std::getenv("M3T_HIP_THREADS")) compact = false;
-    // Region-only batches with >= 1024-bin histograms: the pair table compacted in LDS (round 6; 4096 objects 1.96 ->
-    // 1.78 ms).  While the mixed bins of every object fit the table, that is; histograms that outgrow it by more than
-    // half its size (the kernels report it through a mapped word) go back to the kernel that gathers from L2.
-    // M3T_HIP_COMPACT_TABLE=0 / 1: developer override.
-    // (Region + Depth batches keep the plain kernel: measured with the table, synth512 0.769 / 0.784 vs 0.778 ms -- their
-    // 16-bin pair table is 32 KB and sits in the L1 / L2 anyway, and the depth scan is most of their step)
-    bool compact_table = compact && !roi_frames && ctx->lds_compact_table > 0 && ctx->depth_mods.empty();
-    // (three workgroups per CU instead of four: a batch that is ONE round of the plain kernel but not of this one keeps
-    // the plain kernel -- 1024 objects on 256 CUs: 0.556 vs 0.583 ms; 384: 0.314 / 0.290, 512: 0.325 / 0.298, 2048:
-    // 1.041 / 0.935, 4096: 1.964 / 1.769)
-    if (n > 3 * ctx->compute_cus && n <= 4 * ctx->compute_cus) compact_table = false;
-    if (compact_table && !ctx->table_overflow_host) {
-      void *host = nullptr, *dev = nullptr;
-      HIPCHK(hipHostMalloc(&host, 64, hipHostMallocMapped));
-      std::memset(host, 0, 64);
-      HIPCHK(hipHostGetDevicePointer(&dev, host, 0));
-      ctx->table_overflow_host = static_cast<unsigned*>(host);
-      ctx->table_overflow_dev = static_cast<unsigned*>(dev);
-    }
-    if (compact_table && *static_cast<volatile unsigned*>(ctx->table_overflow_host) > unsigned(ctx->compact_table.table_cap) / 2)
-      compact_table = false;
-    if (const char* e = std::getenv("M3T_HIP_COMPACT_TABLE")) compact_table = compact_table && std::atoi(e) != 0;
-    if (compact_table) ctx->compact_table.table_overflow = ctx->table_overflow_dev;
-    // Batches with depth modalities: 512-thread workgroups, two per CU (round 6).  Their step is the depth scan -- sixteen
-    // lanes per point, 200 points: 12.5 rounds of a 256-thread workgroup, half of that here --, the registers and the LDS
-    // per object stay, 16 waves per CU instead of 12.  Measured (Region + Depth, YCB parameters, ms per step, 256 / 512
-    // threads): 257 objects 0.732 / 0.577, 512: 0.790 / 0.635, 640: 0.970 / 0.949, 700: 0.986 / 1.058, 768: 0.996 / 1.083,
-    // 900: 1.473 / 1.168, 1024: 1.567 / 1.216, 2048: 2.640 / 2.410, 4096: 5.097 / 4.736 -- the 256-thread kernel keeps the
-    // batches that are ONE round of its three workgroups per CU but not of two.  Region-only batches: 384 / 512 objects
-    // 0.314 / 0.295 and 0.324 / 0.306 ms, behind the LDS pair table's 0.286 / 0.292 -- not taken.
-    // M3T_HIP_COMPACT_WIDE=0 / 1: developer override.
-    bool compact_wide = compact && !roi_frames && !compact_table && !ctx->depth_mods.empty() &&
-                        !(2 * n > 5 * ctx->compute_cus && n <= 3 * ctx->compute_cus);
-    if (const char* e = std::getenv("M3T_HIP_COMPACT_WIDE"))
-      compact_wide = compact && !roi_frames && !compact_table && std::atoi(e) != 0;
-    if (roi_frames)
-      ctx->last_step_kernel = split ? "tracking_step_split_guard_kernel"
-                                    : (compact ? "tracking_step_compact_guard_kernel"
-                                               : (ctx->layout.off_hist >= 0 ? "tracking_step_lds_guard_kernel" : "tracking_step_guard_kernel"));
-    else
-    ctx->last_step_kernel = split ? (pair ? "tracking_step_split_pair_kernel" : "tracking_step_split_kernel")
-                                  : (compact ? (compact_table ? "tracking_step_compact_table_kernel"
-                                                              : (compact_wide ? "tracking_step_compact_wide_kernel" : "tracking_step_compact_kernel"))
-                                             : (ctx->layout.off_hist >= 0 ? (pair ? "tracking_step_lds_pair_kernel" : "tracking_step_lds_kernel")
-                                                                          : (pair ? "tracking_step_pair_kernel" : "tracking_step_kernel")));
-    if (compact) {
-      threads = compact_wide ? 2 * M3T_COMPACT_THREADS : M3T_COMPACT_THREADS;
-      histogram_fused = want_fused_histogram && ctx->compact_fuses_histogram;
-    } else if (split) {
-      histogram_fused = want_fused_histogram;
-    }
-    // pass 0: the step; passes 1 (repair) and 2 (the flagged objects again, on whole frames) only behind rectangles
-    for (int pass = 0; pass < (roi_frames ? 2 : 1); ++pass) {
-      if (pass == 1) {
-        for (size_t sl = 0; sl < ctx->roi_sources.size(); ++sl)
-          for (const Ctx::RoiSource& source : ctx->roi_sources[sl]) {
-            const Camera& c0 = *ctx->cameras[source.ids[0]];
-            if (c0.current != int(sl) || !c0.slot_is_roi[sl]) continue;  // (this step reads another slot of these cameras)
-            m3t_roi_rect* rects = ctx->d_roi_rects.as<m3t_roi_rect>() + sl * ctx->cameras.size();
-            hipLaunchKernelGGL(roi_repair_kernel, dim3((c0.intr.height + 7) / 8, unsigned(source.ids.size())), dim3(256), 0,
-                               ctx->stream, source.d_ids, ctx->d_roi_items.as<RoiItemDev>(), ctx->d_roi_item_first.as<int>(),
-                               ctx->d_opts.as<RigidOptDev>(), ctx->roi_n_poses, rects, source.src, source.camera_stride,
-                               source.row_step, c0.frame(int(sl)), c0.frame_bytes, c0.pitch, c0.intr.width, c0.intr.height,
-                               c0.is_depth ? 2 : 3);
-          }
-        guard.mode = 2;
-      }
-      if (compact) {
-        if (roi_frames)
-          hipLaunchKernelGGL(tracking_step_compact_guard_kernel, dim3(n), dim3(threads), ctx->lds_compact, ctx->stream,
-                             ctx->d_opts.as<RigidOptDev>(), ctx->d_region.as<RegionModDev>(),
-                             ctx->d_depth.as<DepthModDev>(), ctx->cams_active, ctx->d_poses.as<float>(), ctx->compact,
-                             iteration, ctx->n_corr_iterations, ctx->n_update_iterations, histogram_fused ? 1 : 0, guard);
-        else if (compact_table)
-          hipLaunchKernelGGL(tracking_step_compact_table_kernel, dim3(n), dim3(threads), ctx->lds_compact_table, ctx->stream,
-                             ctx->d_opts.as<RigidOptDev>(), ctx->d_region.as<RegionModDev>(),
-                             ctx->d_depth.as<DepthModDev>(), ctx->cams_active, ctx->d_poses.as<float>(), ctx->compact_table,
-                             iteration, ctx->n_corr_iterations, ctx->n_update_iterations, histogram_fused ? 1 : 0);
-        else if (compact_wide)
-          hipLaunchKernelGGL(tracking_step_compact_wide_kernel, dim3(n), dim3(threads), ctx->lds_compact, ctx->stream,
-                             ctx->d_opts.as<RigidOptDev>(), ctx->d_region.as<RegionModDev>(),
-                             ctx->d_depth.as<DepthModDev>(), ctx->cams_active, ctx->d_poses.as<float>(), ctx->compact,
-                             iteration, ctx->n_corr_iterations, ctx->n_update_iterations, histogram_fused ? 1 : 0);
-        else
-          hipLaunchKernelGGL(tracking_step_compact_kernel, dim3(n), dim3(threads), ctx->lds_compact, ctx->stream,
-                             ctx->d_opts.as<RigidOptDev>(), ctx->d_region.as<RegionModDev>(),
-                             ctx->d_depth.as<DepthModDev>(), ctx->cams_active, ctx->d_poses.as<float>(), ctx->compact,
-                             iteration, ctx->n_corr_iterations, ctx->n_update_iterations, histogram_fused ? 1 : 0);
-      } else if (split) {
-        SplitParams sp{};
-        if ((r = PrepareSplit(ctx, n, parts, &sp))) return r;
-        if (roi_frames)
-          hipLaunchKernelGGL(tracking_step_split_guard_kernel, dim3((n + 7) / 8 * 8 * parts), dim3(threads), lds_split,
-                             ctx->stream, ctx->d_opts.as<RigidOptDev>(), ctx->d_region.as<RegionModDev>(),
-                             ctx->d_depth.as<DepthModDev>(), ctx->cams_active, ctx->d_poses.as<float>(),
-                             ctx->layout, ctx->off_points, ctx->np_max, iteration, ctx->n_corr_iterations,
-                             ctx->n_update_iterations, ctx->fused_mode == 2 ? 1 : 0, histogram_fused ? 1 : 0, sp, guard);
-        else
-          hipLaunchKernelGGL(split_kernel, dim3((n + 7) / 8 * 8 * parts), dim3(threads), lds_split, ctx->stream,
-                             ctx->d_opts.as<RigidOptDev>(), ctx->d_region.as<RegionModDev>(),
-                             ctx->d_depth.as<DepthModDev>(), ctx->cams_active, ctx->d_poses.as<float>(),
-                             ctx->layout, ctx->off_points, ctx->np_max, iteration, ctx->n_corr_iterations,
-                             ctx->n_update_iterations, ctx->fused_mode == 2 ? 1 : 0, histogram_fused ? 1 : 0, sp);
-      } else if (roi_frames) {
-        hipLaunchKernelGGL(ctx->layout.off_hist >= 0 ? tracking_step_lds_guard_kernel : tracking_step_guard_kernel, dim3(n),
-                           dim3(threads), lds, ctx->stream, ctx->d_opts.as<RigidOptDev>(), ctx->d_region.as<RegionModDev>(),
-                           ctx->d_depth.as<DepthModDev>(), ctx->cams_active, ctx->d_poses.as<float>(),
-                           ctx->layout, ctx->off_points, ctx->np_max, iteration, ctx->n_corr_iterations,
-                           ctx->n_update_iterations, ctx->fused_mode == 2 ? 1 : 0, histogram_fused ? 1 : 0, guard);
-      } else {
-        hipLaunchKernelGGL(kernel, dim3(n), dim3(threads), lds, ctx->stream,
-                           ctx->d_opts.as<RigidOptDev>(), ctx->d_region.as<RegionModDev>(),
-                           ctx->d_depth.as<DepthModDev>(), ctx->cams_active, ctx->d_poses.as<float>(),
-                           ctx->layout, ctx->off_points, ctx->np_max, iteration, ctx->n_corr_iterations,
-                           ctx->n_update_iterations, ctx->fused_mode == 2 ? 1 : 0, histogram_fused ? 1 : 0, 0);
-      }
-      HIPCHK(hipGetLastError());
-    }
-    // (where the repair fetched a whole frame only the device's rectangle table knows it: for the host the slot keeps
-    // counting as a rectangle slot -- conservative -- until the next upload into it)
-    ctx->last_step_shape[0] = n;
-    ctx->last_step_shape[1] = split ? parts : 1;
-    ctx->last_step_shape[2] = threads;
-    ctx->last_step_shape[3] = histogram_fused ? 1 : 0;
-    ctx->state_valid = ctx->fused_mode == 2;
-  } else if (ctx->fused_mode >= 1 && ctx->fused_per_search_possible && !ctx->Distributed() && !ctx->tree_mode &&
-             !std::getenv("M3T_HIP_NO_SEARCH_FUSION")) {
-    // Renderer-fed branches (modelled occlusions, region / silhouette checking): the focused renderings are redrawn
-    // before every correspondence search from the bodies' current poses (correspondence_renderer_ptrs,
-    // tracker.cpp:447-452), so the loop nest runs one search per launch -- the renderers, then ONE launch for the
-    // search and its Newton steps of all objects -- instead of one launch per sub-step: 4 instead of 11 per search.
-    ScopedKernelTimer timer(ctx, 0);
-    const int n = int(ctx->opt_table.size());
-    auto kernel = ctx->layout.off_hist >= 0 ? tracking_step_lds_kernel : tracking_step_kernel;
-    // a batch that leaves CUs idle: several workgroups per object here too (tracking_step_split_render_kernel: the
-    // split kernel with the renderer-fed branches compiled in, one search per launch)
-    int parts = 0;
-    size_t lds_split = 0;
-    bool shared = false;
-    for (auto& m : ctx->region_mods) shared = shared || m->shared_histograms >= 0 || m->p.n_histogram_bins < 4;
-    if (!shared && ctx->split_enabled && ctx->n_corr_iterations < 64 && !std::getenv("M3T_HIP_NO_SPLIT"))
-      parts = ChooseSplitParts(ctx, tracking_step_split_render_kernel, n, M3T_BLOCK_THREADS, false, &lds_split, 16);
-    for (int c = 0; c < ctx->n_corr_iterations; ++c) {
-      if ((r = RenderForModalities(ctx, false))) return r;
-      if (parts >= 2) {
-        SplitParams sp{};
-        if ((r = PrepareSplit(ctx, n, parts, &sp))) return r;
-        hipLaunchKernelGGL(tracking_step_split_render_kernel, dim3((n + 7) / 8 * 8 * parts), dim3(M3T_BLOCK_THREADS),
-                           lds_split, ctx->stream, ctx->d_opts.as<RigidOptDev>(), ctx->d_region.as<RegionModDev>(),
-                           ctx->d_depth.as<DepthModDev>(), ctx->cams_active, ctx->d_poses.as<float>(), ctx->layout,
-                           ctx->off_points, ctx->np_max, iteration, ctx->n_update_iterations,
-                           ctx->fused_mode == 2 ? 1 : 0, c, sp);
-      } else {
-        hipLaunchKernelGGL(kernel, dim3(n), dim3(M3T_BLOCK_THREADS), ctx->lds_track, ctx->stream,
-                           ctx->d_opts.as<RigidOptDev>(), ctx->d_region.as<RegionModDev>(),
-                           ctx->d_depth.as<DepthModDev>(), ctx->cams_active, ctx->d_poses.as<float>(), ctx->layout,
-                           ctx->off_points, ctx->np_max, iteration, 1, ctx->n_update_iterations,
-                           ctx->fused_mode == 2 ? 1 : 0, 0, c);
-      }
-    }
-    HIPCHK(hipGetLastError());
-    ctx->last_step_kernel = parts >= 2 ? "tracking_step_split_render_kernel"
-                                       : (ctx->layout.off_hist >= 0 ? "tracking_step_lds_kernel" : "tracking_step_kernel");
-    ctx->last_step_shape[0] = n;
-    ctx->last_step_shape[1] = parts >= 2 ? parts : 1;
-    ctx->last_step_shape[2] = M3T_BLOCK_THREADS;
-    ctx->last_step_shape[3] = 0;
-    ctx->state_valid = ctx->fused_mode == 2;
-  } else if (TreeStepFused(ctx)) {
-    // kinematic structures: the whole loop nest in one launch, one workgroup per link that carries modalities
-    ScopedKernelTimer timer(ctx, 0);
-    const bool want_fused_histogram = !ctx->region_mods.empty() && ctx->hist_counts_in_lds && ctx->shared_histograms.empty() &&
-                                      !std::getenv("M3T_HIP_NO_FUSED_HISTOGRAM");
-    const size_t lds = TreeStepLds(ctx, want_fused_histogram);
-    if (!ctx->split_abort_host) {
-      void* host = nullptr;
-      HIPCHK(hipHostMalloc(&host, 64, hipHostMallocMapped));
-      std::memset(host, 0, 64);
-      void* dev = nullptr;
-      HIPCHK(hipHostGetDevicePointer(&dev, host, 0));
-      ctx->split_abort_host = static_cast<unsigned*>(host);
-      ctx->split_abort_dev = static_cast<unsigned*>(dev);
-    }
-    if (ctx->tree_seq >= (1u << 26) - 1) {  // the tags restart: clear them first
-      HIPCHK(hipStreamSynchronize(ctx->stream));
-      HIPCHK(hipMemset(ctx->d_tree_exchange.p, 0, ctx->d_tree_exchange.bytes));
-      ctx->tree_seq = 0;
-    }
-    TreeStepParams xp{};
-    xp.seq = ++ctx->tree_seq;
-    if (++ctx->split_launches == 0) ctx->split_launches = 1;
-    xp.abort_id = ctx->split_launches;
-    xp.host_abort = ctx->split_abort_dev;
-    const int off_tree = int((lds / 4 - ctx->tree_block_floats));
-    // Structures that leave CUs idle (the 8-body chain: 8 workgroups on 256 CUs): several workgroups per tracked link
-    // (tracking_step_tree_split_kernel; open structures only -- the constrained kernel keeps one).  The parts of a link
-    // exchange their lines' results, so all workgroups must be resident: checked like the split kernel's launch.
-    int tree_parts = 0;
-    if (!ctx->tree_constrained && ctx->n_corr_iterations < 64 && !std::getenv("M3T_HIP_NO_TREE_SPLIT")) {
-      bool can = true;
-      for (auto& m : ctx->region_mods) can = can && m->shared_histograms < 0 && m->p.n_histogram_bins >= 4;
-      const int elements = std::max(ctx->layout.nl, ctx->depth_mods.empty() ? 1 : ctx->np_max);
-      int limit = 8;  // (the 8-body chain, ms per step: 1 part 0.3046, 2: 0.2939, 4: 0.2756, 8: 0.2649; profiles/r05_chain8_parts.txt)
-      if (const char* e = std::getenv("M3T_HIP_TREE_PARTS")) limit = std::atoi(e);  // developer override
-      for (int p = M3T_SPLIT_MAX_PARTS; can && p >= 2; p >>= 1) {
-        if (p > limit || (elements + p - 1) / p > M3T_SPLIT_LANES / p) continue;
-        if (ctx->tree_split_lds_attribute != lds) {
-          if (hipFuncSetAttribute(reinterpret_cast<const void*>(tracking_step_tree_split_kernel),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, int(lds)) != hipSuccess) {
-            (void)hipGetLastError();
-            break;
-          }
-          ctx->tree_split_lds_attribute = lds;
-        }
-        int resident = ResidentBlocks(ctx, tracking_step_tree_split_kernel, M3T_BLOCK_THREADS, lds);
-        resident = std::min(resident, int(size_t(160) * 1024 / lds));
-        if (resident >= 1 && ctx->n_treesteps * p <= ctx->compute_cus * resident) { tree_parts = p; break; }
-      }
-    }
-    if (tree_parts >= 2) {
-      SplitParams sp{};
-      if ((r = PrepareSplit(ctx, ctx->n_treesteps, tree_parts, &sp))) return r;
-      hipLaunchKernelGGL(tracking_step_tree_split_kernel, dim3(ctx->n_treesteps * tree_parts), dim3(M3T_BLOCK_THREADS), lds,
-                         ctx->stream, ctx->d_treesteps.as<TreeStepDev>(), ctx->d_treeopts.as<TreeOptDev>(),
-                         ctx->d_region.as<RegionModDev>(), ctx->d_depth.as<DepthModDev>(), ctx->cams_active,
-                         ctx->d_poses.as<float>(), ctx->layout, ctx->off_points, ctx->np_max, off_tree, iteration,
-                         ctx->n_corr_iterations, ctx->n_update_iterations, want_fused_histogram ? 1 : 0, xp, sp);
-    } else
-    hipLaunchKernelGGL(ctx->tree_constrained ? tracking_step_tree_constrained_kernel : tracking_step_tree_kernel,
-                       dim3(ctx->n_treesteps), dim3(M3T_BLOCK_THREADS), lds, ctx->stream,
-                       ctx->d_treesteps.as<TreeStepDev>(), ctx->d_treeopts.as<TreeOptDev>(),
-                       ctx->d_region.as<RegionModDev>(), ctx->d_depth.as<DepthModDev>(), ctx->cams_active,
-                       ctx->d_poses.as<float>(), ctx->layout, ctx->off_points, ctx->np_max, off_tree, iteration,
-                       ctx->n_corr_iterations, ctx->n_update_iterations, want_fused_histogram ? 1 : 0, xp);
-    HIPCHK(hipGetLastError());
-    histogram_fused = want_fused_histogram;
-    ctx->links_device_newer = true;
-    ctx->last_step_kernel = tree_parts >= 2 ? "tracking_step_tree_split_kernel"
-                                            : (ctx->tree_constrained ? "tracking_step_tree_constrained_kernel" : "tracking_step_tree_kernel");
-    ctx->last_step_shape[0] = ctx->n_treesteps;
-    ctx->last_step_shape[1] = tree_parts >= 2 ? tree_parts : 1;
-    ctx->last_step_shape[2] = M3T_BLOCK_THREADS;
-    ctx->last_step_shape[3] = histogram_fused ? 1 : 0;
-    ctx->state_valid = false;
-  } else if (TreeStepSegmented(ctx)) {
-    // kinematic structures spread over processes: one launch and one all-reduce (of the link sums) per Newton step,
-    // a last launch for the last solve, the bodies and the histogram update (m3t_links.hip, tree_segment_body)
-    ScopedKernelTimer timer(ctx, 0);
-    const bool want_fused_histogram = !ctx->region_mods.empty() && ctx->hist_counts_in_lds && ctx->shared_histograms.empty() &&
-                                      !std::getenv("M3T_HIP_NO_FUSED_HISTOGRAM");
-    const size_t lds = TreeStepLds(ctx, want_fused_histogram);
-    const int off_tree = int((lds / 4 - ctx->tree_block_floats));
-    auto kernel = ctx->tree_constrained ? tracking_step_tree_segment_constrained_kernel : tracking_step_tree_segment_kernel;
-    float* sums[2] = {ctx->d_link_sums.as<float>(), ctx->d_link_sums_alt.as<float>()};
-    const int n_newton = ctx->n_corr_iterations * ctx->n_update_iterations;
-    // launch k reads the link table launch k - 1 wrote: the primary table at k <= 1 (launch 0 solves nothing and writes
-    // nothing), then alternately; launch k >= 1 writes the other one.  The last launch (k = n_newton) must leave the
-    // joints in the primary table, the one the rest of the library reads: an odd n_newton ends in the second one and
-    // is copied over.
-    // FIRST (the links take their bodies' poses) and FINAL (the bodies take their links') meet in one launch only when
-    // the frame has a single Newton step: a workgroup that starts late would then seed from poses a faster one has
-    // already written back, so that launch seeds from a snapshot taken in front of the loop
-    const float* first_poses = ctx->d_poses.as<float>();
-    if (n_newton == 1) {
-      if (ctx->d_poses_first.bytes < ctx->d_poses.bytes) HIPCHK(ctx->d_poses_first.alloc(ctx->d_poses.bytes));
-      HIPCHK(hipMemcpyAsync(ctx->d_poses_first.p, ctx->d_poses.p, ctx->body_poses.size() * 4, hipMemcpyDeviceToDevice,
-                            ctx->stream));
-      first_poses = ctx->d_poses_first.as<float>();
-    }
-    for (int k = 0; k <= n_newton; ++k) {
-      TreeSegmentParams sp{};
-      const int c = k / std::max(ctx->n_update_iterations, 1), u = k % std::max(ctx->n_update_iterations, 1);
-      const bool last = k == n_newton;
-      int flags = 0;
-      if (k <= 1) flags |= TSEG_FIRST;  // (nothing has written the bodies' link2world yet: launch 0 solves nothing)
-      if (k > 0) flags |= TSEG_SOLVE;
-      if (!last) {
-        flags |= TSEG_SUMS;
-        if (u == 0) flags |= TSEG_SEARCH | (ctx->n_update_iterations > 1 ? TSEG_STORE_STATE : 0);
-        else flags |= TSEG_LOAD_STATE;
-      } else {
-        flags |= TSEG_FINAL;
-      }
-      const bool read_alt = k >= 2 && (k % 2 == 0);
-      const bool write_alt = k >= 1 && (k % 2 == 1);
-      if (read_alt) flags |= TSEG_LINKS_FROM_ALT;
-      if (write_alt) flags |= TSEG_LINKS_TO_ALT;
-      sp.flags = flags;
-      sp.corr_iteration = last ? 0 : c;
-      sp.opt_iteration = last ? 0 : u;
-      sp.sums_in = sums[(k + 1) & 1];  // what launch k - 1 wrote and the all-reduce summed
-      sp.sums_out = sums[k & 1];
-      sp.first_poses = first_poses;
-      hipLaunchKernelGGL(kernel, dim3(ctx->n_treesteps), dim3(M3T_BLOCK_THREADS), lds, ctx->stream,
-                         ctx->d_treesteps.as<TreeStepDev>(), ctx->d_treeopts.as<TreeOptDev>(),
-                         ctx->d_region.as<RegionModDev>(), ctx->d_depth.as<DepthModDev>(), ctx->cams_active,
-                         ctx->d_poses.as<float>(), ctx->layout, ctx->off_points, ctx->np_max, off_tree, iteration,
-                         (last && want_fused_histogram) ? 1 : 0, sp);
-      HIPCHK(hipGetLastError());
-      if (!last) {
-        ctx->partial_ready = true;
-        if ((r = AllReducePartial(ctx, sums[k & 1]))) return r;
-        ctx->partial_ready = false;
-      }
-    }
-    if (n_newton >= 1 && (n_newton % 2 == 1))  // the last launch wrote the second table
-      HIPCHK(hipMemcpyAsync(ctx->d_links.p, ctx->d_links_alt.p, ctx->d_links.bytes, hipMemcpyDeviceToDevice, ctx->stream));
-    histogram_fused = want_fused_histogram;
-    ctx->links_device_newer = true;
-    ctx->last_step_kernel = ctx->tree_constrained ? "tracking_step_tree_segment_constrained_kernel" : "tracking_step_tree_segment_kernel";
-    ctx->last_step_shape[0] = ctx->n_treesteps;
-    ctx->last_step_shape[1] = 1;
-    ctx->last_step_shape[2] = M3T_BLOCK_THREADS;
-    ctx->last_step_shape[3] = histogram_fused ? 1 : 0;
-    ctx->state_valid = false;
-  } else {
-    ctx->last_step_kernel = "";
-    // Tracker::ExecuteTrackingStep tracker.cpp:344-364, one launch per sub-step
-    for (int c = 0; c < ctx->n_corr_iterations; ++c) {
-      if ((r = RenderForModalities(ctx, false))) return r;
-      if ((r = LaunchCorrespondences(ctx, iteration, c))) return r;
-      for (int u = 0; u < ctx->n_update_iterations; ++u) {
-        if ((r = LaunchGradientHessian(ctx, c, u))) return r;
-        if ((r = LaunchOptimization(ctx))) return r;
-      }
-    }
-    ctx->state_valid = true;
-  }
-  if (!histogram_fused) {
+  // the paths (m3t_step_plan.h; DESIGN.md section 5 has the table)
+  StepReport report;
+  std::memcpy(report.shape, ctx->last_step_shape, sizeof(report.shape));  // (the per-sub-step path has no shape of its own)
+  report.state_valid = ctx->state_valid;
+  if (rigid_fused)  // (a communicator: the structures span GPUs)
+    r = StepRigidFused(ctx, iteration, overrides, roi_frames, &report);
+  else if (ctx->fused_mode >= 1 && ctx->fused_per_search_possible && !ctx->Distributed() && !ctx->tree_mode &&
+           !overrides.no_search_fusion)
+    r = StepPerSearch(ctx, iteration, overrides, &report);
+  else if (TreeStepFused(ctx, overrides))
+    r = StepTreeFused(ctx, iteration, overrides, &report);
+  else if (TreeStepSegmented(ctx, overrides))
+    r = StepTreeSegmented(ctx, iteration, overrides, &report);
+  else
+    r = StepSubSteps(ctx, iteration, &report);
+  ctx->last_step_kernel = report.kernel;
+  std::memcpy(ctx->last_step_shape, report.shape, sizeof(report.shape));
+  ctx->state_valid = report.state_valid;
+  if (report.links_device_newer) ctx->links_device_newer = true;
+  if (r) return r;
+  if (!report.histogram_fused) {
     if ((r = RenderForModalities(ctx, true))) return r;
     if ((r = LaunchHistogram(ctx, iteration, false, roi_frames))) return r;
   }
@@ -5203,13 +5194,13 @@ int m3t_hip_comm_get_rank_count(m3t_hip_context* ctx, int* n_ranks) {
 int m3t_hip_get_step_kernel(m3t_hip_context* ctx, char* name, size_t capacity) {
   CHECK_CTX();
   REQUIRE(name && capacity > 0, M3T_ERR_INVALID_ARGUMENT, "null output");
-  std::snprintf(name, capacity, "%s", ctx->last_step_kernel);
+  std::snprintf(name, capacity, "%s", m3t_step::StepKernelName(m3t_step::ReportedStepKernel(ctx->last_step_kernel)));
   return M3T_OK;
 }
 int m3t_hip_get_step_variant(m3t_hip_context* ctx, char* name, size_t capacity) {
   CHECK_CTX();
   REQUIRE(name && capacity > 0, M3T_ERR_INVALID_ARGUMENT, "null output");
-  std::snprintf(name, capacity, "%s", ctx->last_step_moments_first ? "tracking_step_split_moments_kernel" : ctx->last_step_kernel);
+  std::snprintf(name, capacity, "%s", m3t_step::StepKernelName(ctx->last_step_kernel));
   return M3T_OK;
 }
 int m3t_hip_get_kernel_timing(m3t_hip_context* ctx, float total_ms[2], int launches[2]) {

@@ -8,7 +8,7 @@ oracle bit for bit.
 A case says how to make its inputs, which parameters the modalities and the tracker get, what the oracle must show,
 and -- `expect` -- which kernel the host has to launch in every launch shape.  The expected names are written down
 from the host's rules in m3t_hip_api.hip (UploadTables: compact_possible, split_possible; ComputeLayout: layout.off_hist,
-lds_compact_table; ChooseSplitParts; LaunchTrackingStep), in `_expect` below:
+lds_compact_table) and m3t_step_plan.h (RigidSplitParts, PlanRigidStep), in `_expect` below:
 
   * compact shapes need function_length 8, distribution_length 12, n_lines_max <= 256 (M3T_COMPACT_THREADS) and every
     scale in 1..9; otherwise the one-workgroup kernel is launched (512 threads);
@@ -300,8 +300,8 @@ def mixed_bins(hist_f, hist_b):
 
 def table_kernels(ref, n_frames):
     """the kernel of every frame in the "compact_cap64" shape, from the oracle's histograms and the host's rule
-    (LaunchTrackingStep): every workgroup whose object has more mixed bins than the table holds walks with the global
-    table and reports by how much; once a report exceeds half the table, the host launches the kernel without the table
+    (m3t_step_plan.h, PlanRigidStep): every workgroup whose object has more mixed bins than the table holds walks with
+    the global table and reports by how much; once a report exceeds half the table, the host launches the kernel without the table
     until StartModalities brings new histograms"""
     out, worst = [], 0
     for k in range(n_frames):
