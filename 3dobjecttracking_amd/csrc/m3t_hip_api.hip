@@ -24,6 +24,7 @@
 #include "m3t_device.h"
 #include "m3t_view_rows.h"
 #include "m3t_step_plan.h"
+#include "m3t_call_args.h"
 #include "m3t_kernels.hip"
 #include "m3t_judge.hip"
 #include "m3t_opt.hip"
@@ -64,6 +65,42 @@ struct DevMem {
   }
   template <typename T>
   T* as() const { return static_cast<T*>(p); }
+};
+
+// Blocks of mapped host memory taken in turn by enqueued calls: a call fills its block, its launches read it in place, and
+// the call kDepth calls later waits for them before it takes the block again.
+struct MappedRing {
+  static constexpr int kDepth = 4;
+  void* block[kDepth] = {nullptr};
+  size_t bytes[kDepth] = {0};
+  hipEvent_t done[kDepth] = {nullptr};
+  int next = 0;
+  MappedRing() = default;
+  MappedRing(const MappedRing&) = delete;
+  MappedRing& operator=(const MappedRing&) = delete;
+  ~MappedRing() {
+    for (int i = 0; i < kDepth; ++i) {
+      if (block[i]) (void)hipHostFree(block[i]);
+      if (done[i]) (void)hipEventDestroy(done[i]);
+    }
+  }
+  hipError_t Acquire(size_t n, void** host, void** dev, int* slot) {
+    const int s = *slot = next;
+    next = (s + 1) % kDepth;
+    hipError_t e = hipSuccess;
+    if (!done[s] && (e = hipEventCreateWithFlags(&done[s], hipEventDisableTiming)) != hipSuccess) return e;
+    if ((e = hipEventSynchronize(done[s])) != hipSuccess) return e;  // the call kDepth calls ago: normally long complete
+    if (bytes[s] < n) {
+      if (block[s] && (e = hipHostFree(block[s])) != hipSuccess) return e;
+      block[s] = nullptr;
+      bytes[s] = 0;
+      if ((e = hipHostMalloc(&block[s], n * 2, hipHostMallocMapped)) != hipSuccess) return e;
+      bytes[s] = n * 2;
+    }
+    *host = block[s];
+    return hipHostGetDevicePointer(dev, block[s], 0);
+  }
+  hipError_t Release(int slot, hipStream_t stream) { return hipEventRecord(done[slot], stream); }
 };
 
 struct Model {
@@ -180,7 +217,6 @@ struct Optimizer {
 };
 
 struct Judge {  // m3t_hip_judge_*: the evaluators' judgement of a list of bodies, rows of results in mapped host memory
-  static constexpr int kStage = 4;
   std::vector<int> body_ids;
   int n_rows_max = 0, n_rows = 0;
   float thr_t = 0.05f, thr_r = 5.0f * 3.14159265358979323846f / 180.0f;  // rbot_evaluator.h:192-193
@@ -198,11 +234,7 @@ struct Judge {  // m3t_hip_judge_*: the evaluators' judgement of a list of bodie
   m3t_body_judgement* rows_host = nullptr;  // [n_rows_max][n_bodies], written by the kernels in place
   m3t_body_judgement* rows_dev = nullptr;
   std::vector<hipEvent_t> row_done;         // per row: behind the launches of its call
-  // the ground-truth poses and the region-modality lists of a call, read in place by its launches
-  void* stage[kStage] = {nullptr};
-  size_t stage_bytes[kStage] = {0};
-  hipEvent_t stage_done[kStage] = {nullptr};
-  int stage_next = 0;
+  MappedRing args;  // the ground-truth poses and the region-modality lists of a call, read in place by its launches
   // m3t_hip_judge_set_structures: the structures' groups of listed bodies and a second table of rows
   int n_structures = 0;
   DevMem d_structure_ints, d_structure_thresholds;  // [first group of each structure | first index of each group | indices]
@@ -214,10 +246,6 @@ struct Judge {  // m3t_hip_judge_*: the evaluators' judgement of a list of bodie
     if (structure_rows_host) (void)hipHostFree(structure_rows_host);
     for (auto& e : row_done)
       if (e) (void)hipEventDestroy(e);
-    for (int i = 0; i < kStage; ++i) {
-      if (stage[i]) (void)hipHostFree(stage[i]);
-      if (stage_done[i]) (void)hipEventDestroy(stage_done[i]);
-    }
   }
 };
 
@@ -376,12 +404,7 @@ struct m3t_hip_context {
   size_t cam_stage_bytes = 0;
   hipEvent_t cam_stage_done[kStage] = {nullptr};
   int cam_stage_next = 0;
-  // m3t_hip_reset_bodies: the call's lists and poses, in mapped host memory the two launches read in place
-  static constexpr int kResetStage = 4;
-  void* reset_stage[kResetStage] = {nullptr};
-  size_t reset_stage_bytes[kResetStage] = {0};
-  hipEvent_t reset_stage_done[kResetStage] = {nullptr};
-  int reset_stage_next = 0;
+  MappedRing reset_args;  // m3t_hip_reset_bodies / _structures: the call's lists and poses, read in place by its launches
   std::vector<std::unique_ptr<Judge>> judges;  // m3t_hip_judge_create
   // asynchronous ingest: frame copies run on their own stream beside the tracking kernels
   static constexpr int kStepEvents = 16;
@@ -1912,6 +1935,107 @@ DepthMod* GetDepth(Ctx* ctx, int id) {
   return ctx->depth_mods[ctx->modalities[id].index].get();
 }
 
+// ---- what the enqueued calls share (m3t_hip_reset_bodies, m3t_hip_reset_structures, m3t_hip_judge_bodies): validate ->
+// collect -> BeginEnqueued -> acquire a block of a MappedRing and fill it (m3t_call_args.h) -> launches -> host mirrors
+// -> EndEnqueued
+
+// n ids below limit, none of them twice; listed: the mask of those named
+int CheckListedIds(Ctx* ctx, const char* entry, const int* ids, int n, int limit, const char* what, std::vector<char>* listed) {
+  listed->assign(size_t(limit), 0);
+  for (int i = 0; i < n; ++i) {
+    REQUIRE(ids[i] >= 0 && ids[i] < limit, M3T_ERR_INVALID_ARGUMENT, std::string(entry) + ": bad " + what + " id");
+    REQUIRE(!(*listed)[size_t(ids[i])], M3T_ERR_INVALID_ARGUMENT,
+            std::string(entry) + (std::strchr("aeiou", what[0]) ? ": an " : ": a ") + what + " id is listed twice");
+    (*listed)[size_t(ids[i])] = 1;
+  }
+  return M3T_OK;
+}
+// What the modalities of the listed bodies read: region modalities in table order, their start-modality renderers and
+// shared ColorHistograms (each once, in the order met), the cameras of all their modalities (as often as read).
+struct BodiesRead { std::vector<int> region_ids, renderer_ids, cameras, shared_ids; };
+BodiesRead CollectReads(Ctx* ctx, const std::vector<char>& listed) {
+  BodiesRead out;
+  auto add_once = [](std::vector<int>* v, int id) {
+    if (id >= 0 && std::find(v->begin(), v->end(), id) == v->end()) v->push_back(id);
+  };
+  for (size_t i = 0; i < ctx->region_mods.size(); ++i) {
+    const RegionMod& m = *ctx->region_mods[i];
+    if (!listed[size_t(m.body)]) continue;
+    add_once(&out.shared_ids, m.shared_histograms);
+    out.region_ids.push_back(int(i));
+    out.cameras.push_back(m.camera);
+    if (m.depth_camera >= 0) out.cameras.push_back(m.depth_camera);
+    add_once(&out.renderer_ids, m.dev.model_occlusions ? m.depth_renderer : -1);
+    add_once(&out.renderer_ids, m.dev.use_region_checking ? m.silhouette_renderer : -1);
+  }
+  for (auto& m : ctx->depth_mods)
+    if (listed[size_t(m->body)]) out.cameras.push_back(m->camera);
+  return out;
+}
+// Launches outside the fused step read the current frames of these cameras unguarded: outside the trackers' rectangle a
+// slot filled by ROI ingest holds whatever an earlier frame left there, and a body reset between two steps reads its
+// histogram pixels away from the rectangle of its old pose.  Refused: the caller uploads the whole frame first (m3t_hip.h).
+template <typename Cameras>
+int RefuseRoiFrames(Ctx* ctx, const Cameras& cameras, const char* entry) {
+  for (int c : cameras)
+    REQUIRE(c < 0 || !ctx->cameras[c]->slot_is_roi[ctx->cameras[c]->current], M3T_ERR_UNSUPPORTED,
+            std::string(entry) + ": a frame slot the modalities read holds the trackers' rectangle only (ROI ingest); "
+            "upload the whole frame into it first (camera_upload_slot)");
+  return M3T_OK;
+}
+// ... for the sub-steps outside the fused step (start_modalities, calculate_correspondences, calculate_results)
+int RequireWholeFrames(Ctx* ctx, const char* entry) {
+  int r = M3T_OK;
+  for (auto& m : ctx->region_mods)
+    if ((r = RefuseRoiFrames(ctx, std::array<int, 2>{m->camera, m->depth_camera}, entry))) return r;
+  for (auto& m : ctx->depth_mods)
+    if ((r = RefuseRoiFrames(ctx, std::array<int, 1>{m->camera}, entry))) return r;
+  return M3T_OK;
+}
+// (tables and poses that were waiting for their upload anyway)  changes_state: not a judgement without reset
+int BeginEnqueued(Ctx* ctx, bool changes_state) {
+  HIPCHK(hipSetDevice(ctx->device));
+  const bool untracked_before = ctx->untracked_launches;
+  if (changes_state && ctx->poses_dirty_host) ctx->roi_end_valid = false;  // poses set by the host: the last step's end no longer vouches for them
+  int r = Prepare(ctx, changes_state);
+  if (r) return r;
+  ctx->untracked_launches = untracked_before;  // reads poses only, or is tracked by the step_done event of EndEnqueued
+  return M3T_OK;
+}
+// cameras: whose current frames the call's launches read (null: none)
+int EndEnqueued(Ctx* ctx, MappedRing* ring, int slot, const std::vector<int>* cameras) {
+  HIPCHK(hipGetLastError());
+  HIPCHK(ring->Release(slot, ctx->stream));
+  if (cameras && ctx->async_ingest) {  // a later asynchronous upload into a slot these launches read waits for them
+    HIPCHK(hipEventRecord(ctx->step_done[ctx->step_counter % Ctx::kStepEvents], ctx->stream));
+    for (int c : *cameras) ctx->cameras[c]->last_read_step[ctx->cameras[c]->current] = ctx->step_counter;
+    ++ctx->step_counter;
+  }
+  return M3T_OK;
+}
+// the start-modality renderers of a call, from the two lists in its argument block
+int LaunchStartRenderers(Ctx* ctx, const std::vector<int>& renderer_ids, const int* d_ids, const int* d_pairs) {
+  if (renderer_ids.empty()) return M3T_OK;
+  int largest = 0;
+  for (int id : renderer_ids) {
+    ctx->renderers[size_t(id)]->rendered = true;
+    largest = std::max(largest, ctx->renderers[size_t(id)]->image_size);
+  }
+  return LaunchRenderers(ctx, d_ids, int(renderer_ids.size()), d_pairs, int(renderer_ids.size()), largest);
+}
+Judge* GetJudge(Ctx* ctx, int id, const char* entry) {
+  if (id >= 0 && id < int(ctx->judges.size())) return ctx->judges[size_t(id)].get();
+  Fail(ctx, M3T_ERR_INVALID_ARGUMENT, std::string(entry) + ": bad judge id");
+  return nullptr;
+}
+// xyz as float4, padded to a multiple with copies of vertex 0 (which change no minimum and form pairs of the set only)
+std::vector<float> PadVertices(const float* xyz, int n, size_t multiple) {
+  const size_t n_padded = (size_t(n) + multiple - 1) / multiple * multiple;
+  std::vector<float> padded(n_padded * 4, 0.0f);
+  for (size_t i = 0; i < n_padded; ++i) std::memcpy(&padded[4 * i], xyz + 3 * (i < size_t(n) ? i : 0), 12);
+  return padded;
+}
+
 // The context's streams.  With CUs reserved for ingest (m3t_hip_reserve_ingest_cus) the compute stream runs on the
 // CUs of mask bits [0, CUs - n) and copy stream 0 -- the one the ROI pull kernel is launched on -- on bits
 // [CUs - n, CUs).  Bit i of a mask belongs to XCD i mod 8 (amdkfd deals the bits round-robin; tools/ubench_cumask.hip
@@ -1984,10 +2108,6 @@ void m3t_hip_destroy(m3t_hip_context* ctx) {
   for (int i = 0; i < m3t_hip_context::kStage; ++i) {
     if (ctx->cam_stage[i]) (void)hipHostFree(ctx->cam_stage[i]);
     if (ctx->cam_stage_done[i]) (void)hipEventDestroy(ctx->cam_stage_done[i]);
-  }
-  for (int i = 0; i < m3t_hip_context::kResetStage; ++i) {
-    if (ctx->reset_stage[i]) (void)hipHostFree(ctx->reset_stage[i]);
-    if (ctx->reset_stage_done[i]) (void)hipEventDestroy(ctx->reset_stage_done[i]);
   }
   for (auto& c : ctx->cameras)
     for (auto& e : c->slot_copied)
@@ -3740,21 +3860,6 @@ int m3t_hip_set_object_split(m3t_hip_context* ctx, int enable) {
   return M3T_OK;
 }
 
-// The sub-steps outside the fused step (start_modalities, calculate_correspondences, calculate_results) read the
-// modalities' current frames unguarded: outside the trackers' rectangle a slot filled by ROI ingest holds whatever an
-// earlier frame left there -- and a body reset between two steps reads its histogram pixels around the new pose, away
-// from the rectangle of the old one.  Refused; the caller uploads the whole frame into the slot first (m3t_hip.h).
-static int RequireWholeFrames(Ctx* ctx, const char* entry) {
-  auto roi = [ctx](int c) { return c >= 0 && ctx->cameras[c]->slot_is_roi[ctx->cameras[c]->current]; };
-  bool roi_frames = false;
-  for (auto& m : ctx->region_mods) roi_frames = roi_frames || roi(m->camera) || roi(m->depth_camera);
-  for (auto& m : ctx->depth_mods) roi_frames = roi_frames || roi(m->camera);
-  REQUIRE(!roi_frames, M3T_ERR_UNSUPPORTED,
-          std::string(entry) + ": a frame slot the modalities read holds the trackers' rectangle only (ROI ingest); "
-          "upload the whole frame into it first (camera_upload_slot)");
-  return M3T_OK;
-}
-
 int m3t_hip_start_modalities(m3t_hip_context* ctx, int iteration) {
   CHECK_CTX();
   HIPCHK(hipSetDevice(ctx->device));
@@ -3782,105 +3887,48 @@ int m3t_hip_reset_bodies(m3t_hip_context* ctx, const int* body_ids, const float*
   REQUIRE(n >= 0, M3T_ERR_INVALID_ARGUMENT, "reset_bodies: n must not be negative");
   if (n == 0) return M3T_OK;
   REQUIRE(body_ids, M3T_ERR_INVALID_ARGUMENT, "reset_bodies: null body ids");
-  const int n_all = int(ctx->body_poses.size() / 16);
-  std::vector<char> listed(size_t(n_all), 0);
-  for (int i = 0; i < n; ++i) {
-    REQUIRE(body_ids[i] >= 0 && body_ids[i] < n_all, M3T_ERR_INVALID_ARGUMENT, "reset_bodies: bad body id");
-    REQUIRE(!listed[body_ids[i]], M3T_ERR_INVALID_ARGUMENT, "reset_bodies: a body id is listed twice");
-    listed[body_ids[i]] = 1;
-  }
+  std::vector<char> listed;
+  int r = CheckListedIds(ctx, "reset_bodies", body_ids, n, int(ctx->body_poses.size() / 16), "body", &listed);
+  if (r) return r;
   for (auto& l : ctx->links)
     REQUIRE(l.body < 0 || !listed[l.body] || (l.parent < 0 && l.children.empty()), M3T_ERR_UNSUPPORTED,
             "reset_bodies: a listed body belongs to a structure of more than one link (set the poses of the "
             "structure and call start_modalities)");
-  std::vector<int> region_ids, renderer_ids, cameras;
-  for (size_t i = 0; i < ctx->region_mods.size(); ++i) {
-    const RegionMod& m = *ctx->region_mods[i];
-    if (!listed[m.body]) continue;
-    REQUIRE(m.shared_histograms < 0, M3T_ERR_UNSUPPORTED,
-            "reset_bodies: a region modality of a listed body uses shared ColorHistograms (call start_modalities)");
-    region_ids.push_back(int(i));
-    cameras.push_back(m.camera);
-    if (m.depth_camera >= 0) cameras.push_back(m.depth_camera);
-    for (int renderer : {m.dev.model_occlusions ? m.depth_renderer : -1, m.dev.use_region_checking ? m.silhouette_renderer : -1})
-      if (renderer >= 0 && std::find(renderer_ids.begin(), renderer_ids.end(), renderer) == renderer_ids.end())
-        renderer_ids.push_back(renderer);
-  }
-  for (auto& m : ctx->depth_mods)
-    if (listed[m->body]) cameras.push_back(m->camera);
-  for (int c : cameras)  // (the same refusal as RequireWholeFrames, for the cameras these bodies' modalities read)
-    REQUIRE(!ctx->cameras[c]->slot_is_roi[ctx->cameras[c]->current], M3T_ERR_UNSUPPORTED,
-            "reset_bodies: a frame slot the modalities read holds the trackers' rectangle only (ROI ingest); "
-            "upload the whole frame into it first (camera_upload_slot)");
-  HIPCHK(hipSetDevice(ctx->device));
-  const bool untracked_before = ctx->untracked_launches;
-  if (ctx->poses_dirty_host) ctx->roi_end_valid = false;  // poses set by the host: the last step's end no longer vouches for them
-  int r = Prepare(ctx, true);  // (tables and poses that were waiting for their upload anyway)
-  if (r) return r;
-  ctx->untracked_launches = untracked_before;  // tracked by a step_done event below
-  // the call's arguments: [body ids][region modality ids][renderer ids][{renderer, -1} pairs][poses]
-  const size_t n_region = region_ids.size(), n_render = renderer_ids.size();
-  const size_t ints = size_t(n) + n_region + 3 * n_render;
-  const size_t off_poses = (ints * 4 + 15) / 16 * 16;
-  const size_t bytes = off_poses + (body2world_poses ? size_t(n) * 64 : 0);
-  const int stage = ctx->reset_stage_next;
-  ctx->reset_stage_next = (stage + 1) % Ctx::kResetStage;
-  if (!ctx->reset_stage_done[stage]) HIPCHK(hipEventCreateWithFlags(&ctx->reset_stage_done[stage], hipEventDisableTiming));
-  HIPCHK(hipEventSynchronize(ctx->reset_stage_done[stage]));  // the call four resets ago: normally long complete
-  if (ctx->reset_stage_bytes[stage] < bytes) {
-    if (ctx->reset_stage[stage]) HIPCHK(hipHostFree(ctx->reset_stage[stage]));
-    ctx->reset_stage[stage] = nullptr;
-    ctx->reset_stage_bytes[stage] = 0;
-    HIPCHK(hipHostMalloc(&ctx->reset_stage[stage], bytes * 2, hipHostMallocMapped));
-    ctx->reset_stage_bytes[stage] = bytes * 2;
-  }
-  int* h_ints = static_cast<int*>(ctx->reset_stage[stage]);
-  std::memcpy(h_ints, body_ids, size_t(n) * 4);
-  if (n_region) std::memcpy(h_ints + n, region_ids.data(), n_region * 4);
-  for (size_t k = 0; k < n_render; ++k) {
-    h_ints[size_t(n) + n_region + k] = renderer_ids[k];
-    h_ints[size_t(n) + n_region + n_render + 2 * k] = renderer_ids[k];
-    h_ints[size_t(n) + n_region + n_render + 2 * k + 1] = -1;
-  }
-  if (body2world_poses) std::memcpy(static_cast<uint8_t*>(ctx->reset_stage[stage]) + off_poses, body2world_poses, size_t(n) * 64);
-  void* dev = nullptr;
-  HIPCHK(hipHostGetDevicePointer(&dev, ctx->reset_stage[stage], 0));
-  const int* d_ints = static_cast<const int*>(dev);
-  const float* d_new_poses = body2world_poses ? reinterpret_cast<const float*>(static_cast<const uint8_t*>(dev) + off_poses) : nullptr;
-  const int items = std::max(body2world_poses ? n * 16 : 0, int(n_region));
+  const BodiesRead reads = CollectReads(ctx, listed);
+  REQUIRE(reads.shared_ids.empty(), M3T_ERR_UNSUPPORTED,
+          "reset_bodies: a region modality of a listed body uses shared ColorHistograms (call start_modalities)");
+  if ((r = RefuseRoiFrames(ctx, reads.cameras, "reset_bodies")) || (r = BeginEnqueued(ctx, true))) return r;
+  const int n_region = int(reads.region_ids.size());
+  const m3t_args::ResetBodiesArgs args(size_t(n), reads.region_ids.size(), reads.renderer_ids.size(), body2world_poses != nullptr);
+  void *host = nullptr, *dev = nullptr;
+  int slot = 0;
+  HIPCHK(ctx->reset_args.Acquire(args.bytes, &host, &dev, &slot));
+  m3t_args::PutInts(host, args.body_ids, body_ids);
+  m3t_args::PutInts(host, args.region_ids, reads.region_ids.data());
+  m3t_args::PutRenderers(host, args.renderer_ids, args.renderer_pairs, reads.renderer_ids.data());
+  m3t_args::PutPoses(host, args.poses, body2world_poses);
+  const int* d_region_ids = args.region_ids.in<int>(dev);
+  const int items = std::max(body2world_poses ? n * 16 : 0, n_region);
   if (items > 0)
     hipLaunchKernelGGL(reset_bodies_scatter_kernel, dim3((items + 255) / 256), dim3(256), 0, ctx->stream,
-                       ctx->d_poses.as<float>(), d_ints, d_new_poses, n, ctx->d_region.as<RegionModDev>(), d_ints + n,
-                       int(n_region), iteration);
+                       ctx->d_poses.as<float>(), args.body_ids.in<int>(dev),
+                       body2world_poses ? args.poses.in<float>(dev) : (const float*)nullptr, n,
+                       ctx->d_region.as<RegionModDev>(), d_region_ids, n_region, iteration);
   // the host mirrors follow (the poses' only where the host copy counts: the device stays authoritative)
   if (body2world_poses) {
     for (int i = 0; i < n; ++i) std::memcpy(&ctx->body_poses[size_t(body_ids[i]) * 16], body2world_poses + size_t(i) * 16, 64);
     ctx->roi_end_valid = false;  // the next step's rectangles start from a snapshot of these poses
   }
-  for (int id : region_ids) ctx->region_mods[id]->dev.first_iteration = iteration;
-  if (n_render) {
-    int largest = 0;
-    for (int id : renderer_ids) {
-      ctx->renderers[id]->rendered = true;
-      largest = std::max(largest, ctx->renderers[id]->image_size);
-    }
-    if ((r = LaunchRenderers(ctx, d_ints + n + n_region, int(n_render), d_ints + n + n_region + n_render, int(n_render), largest)))
-      return r;
-  }
+  for (int id : reads.region_ids) ctx->region_mods[id]->dev.first_iteration = iteration;
+  if ((r = LaunchStartRenderers(ctx, reads.renderer_ids, args.renderer_ids.in<int>(dev), args.renderer_pairs.in<int>(dev))))
+    return r;
   if (n_region) {
     ScopedKernelTimer timer(ctx, 1);
     hipLaunchKernelGGL(region_histogram_list_kernel, dim3(unsigned(n_region)), dim3(M3T_BLOCK_THREADS), ctx->lds_hist,
-                       ctx->stream, ctx->d_region.as<RegionModDev>(), d_ints + n, ctx->cams_active,
+                       ctx->stream, ctx->d_region.as<RegionModDev>(), d_region_ids, ctx->cams_active,
                        ctx->d_poses.as<float>(), ctx->hist_counts_in_lds ? 1 : 0);
   }
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(ctx->reset_stage_done[stage], ctx->stream));
-  if (ctx->async_ingest) {  // a later asynchronous upload into a slot these launches read waits for them
-    HIPCHK(hipEventRecord(ctx->step_done[ctx->step_counter % Ctx::kStepEvents], ctx->stream));
-    for (int c : cameras) ctx->cameras[c]->last_read_step[ctx->cameras[c]->current] = ctx->step_counter;
-    ++ctx->step_counter;
-  }
-  return M3T_OK;
+  return EndEnqueued(ctx, &ctx->reset_args, slot, &reads.cameras);
 }
 // RTBEvaluator::SetBodyAndJointPoses (rtb_evaluator.cpp:809-858) + Tracker::StartModalities (tracker.cpp:430-445) for n
 // kinematic structures of the batch and for no other: the bodies' poses, the joints that follow from them, the
@@ -3893,14 +3941,9 @@ int m3t_hip_reset_structures(m3t_hip_context* ctx, const int* optimizer_ids, int
   if (n == 0) return M3T_OK;
   REQUIRE(optimizer_ids && body2world_poses, M3T_ERR_INVALID_ARGUMENT, "reset_structures: null optimizer ids or poses");
   REQUIRE(mode == 0 || mode == 1, M3T_ERR_INVALID_ARGUMENT, "reset_structures: mode must be 0 (independent / projected) or 1 (constrained)");
-  const int n_opts = int(ctx->optimizers.size());
-  const int n_all = int(ctx->body_poses.size() / 16);
-  std::vector<char> opt_listed(size_t(n_opts), 0), listed(size_t(n_all), 0);
-  for (int i = 0; i < n; ++i) {
-    REQUIRE(optimizer_ids[i] >= 0 && optimizer_ids[i] < n_opts, M3T_ERR_INVALID_ARGUMENT, "reset_structures: bad optimizer id");
-    REQUIRE(!opt_listed[optimizer_ids[i]], M3T_ERR_INVALID_ARGUMENT, "reset_structures: an optimizer id is listed twice");
-    opt_listed[optimizer_ids[i]] = 1;
-  }
+  std::vector<char> opt_listed, listed(ctx->body_poses.size() / 16, 0);
+  int r = CheckListedIds(ctx, "reset_structures", optimizer_ids, n, int(ctx->optimizers.size()), "optimizer", &opt_listed);
+  if (r) return r;
   REQUIRE(!ctx->Distributed(), M3T_ERR_UNSUPPORTED,
           "reset_structures: the context's structures are spread over ranks (a communicator or a reduce callback is set)");
   // the structures' links in table order (depth first, parents before children) and what each of them takes
@@ -3941,107 +3984,51 @@ int m3t_hip_reset_structures(m3t_hip_context* ctx, const int* optimizer_ids, int
       entries.push_back(e);
     }
   }
-  std::vector<int> region_ids, renderer_ids, cameras, shared_ids;
-  for (size_t i = 0; i < ctx->region_mods.size(); ++i) {
-    const RegionMod& m = *ctx->region_mods[i];
-    if (!listed[size_t(m.body)]) continue;
-    if (m.shared_histograms >= 0 && std::find(shared_ids.begin(), shared_ids.end(), m.shared_histograms) == shared_ids.end())
-      shared_ids.push_back(m.shared_histograms);
-    region_ids.push_back(int(i));
-    cameras.push_back(m.camera);
-    if (m.depth_camera >= 0) cameras.push_back(m.depth_camera);
-    for (int renderer : {m.dev.model_occlusions ? m.depth_renderer : -1, m.dev.use_region_checking ? m.silhouette_renderer : -1})
-      if (renderer >= 0 && std::find(renderer_ids.begin(), renderer_ids.end(), renderer) == renderer_ids.end())
-        renderer_ids.push_back(renderer);
-  }
+  const BodiesRead reads = CollectReads(ctx, listed);
   for (auto& m : ctx->region_mods)
     REQUIRE(m->shared_histograms < 0 || listed[size_t(m->body)] ||
-                std::find(shared_ids.begin(), shared_ids.end(), m->shared_histograms) == shared_ids.end(),
+                std::find(reads.shared_ids.begin(), reads.shared_ids.end(), m->shared_histograms) == reads.shared_ids.end(),
             M3T_ERR_UNSUPPORTED,
             "reset_structures: shared ColorHistograms of a listed structure are also used by a modality of a structure "
             "that is not listed (the reference defines no result for that)");
-  for (auto& m : ctx->depth_mods)
-    if (listed[size_t(m->body)]) cameras.push_back(m->camera);
-  for (int c : cameras)  // (the refusal of reset_bodies, for the cameras these structures' modalities read)
-    REQUIRE(!ctx->cameras[c]->slot_is_roi[ctx->cameras[c]->current], M3T_ERR_UNSUPPORTED,
-            "reset_structures: a frame slot the modalities read holds the trackers' rectangle only (ROI ingest); "
-            "upload the whole frame into it first (camera_upload_slot)");
-  HIPCHK(hipSetDevice(ctx->device));
-  const bool untracked_before = ctx->untracked_launches;
-  if (ctx->poses_dirty_host) ctx->roi_end_valid = false;
-  int r = Prepare(ctx, true);  // (tables and poses that were waiting for their upload anyway)
-  if (r) return r;
-  ctx->untracked_launches = untracked_before;  // tracked by a step_done event below
+  if ((r = RefuseRoiFrames(ctx, reads.cameras, "reset_structures")) || (r = BeginEnqueued(ctx, true))) return r;
   if (!ctx->tree_mode)
     for (auto& s : structures) s.opt = -1;  // free rigid bodies only: there is no link table, the poses are all
-  // the call's arguments: [structures][links][region modality ids][renderer ids][{renderer, -1} pairs][poses]
-  const size_t n_poses = pose_body.size(), n_region = region_ids.size(), n_render = renderer_ids.size();
   static_assert(sizeof(StructureResetDev) == 12 && sizeof(StructureLinkResetDev) == 12, "lists of ints");
-  const size_t off_entries = structures.size() * 3, off_region = off_entries + entries.size() * 3,
-               off_render = off_region + n_region, off_pairs = off_render + n_render, ints = off_pairs + 2 * n_render;
-  const size_t off_poses = (ints * 4 + 15) / 16 * 16;
-  const size_t bytes = off_poses + n_poses * 64;
-  const int stage = ctx->reset_stage_next;
-  ctx->reset_stage_next = (stage + 1) % Ctx::kResetStage;
-  if (!ctx->reset_stage_done[stage]) HIPCHK(hipEventCreateWithFlags(&ctx->reset_stage_done[stage], hipEventDisableTiming));
-  HIPCHK(hipEventSynchronize(ctx->reset_stage_done[stage]));  // the call four resets ago: normally long complete
-  if (ctx->reset_stage_bytes[stage] < bytes) {
-    if (ctx->reset_stage[stage]) HIPCHK(hipHostFree(ctx->reset_stage[stage]));
-    ctx->reset_stage[stage] = nullptr;
-    ctx->reset_stage_bytes[stage] = 0;
-    HIPCHK(hipHostMalloc(&ctx->reset_stage[stage], bytes * 2, hipHostMallocMapped));
-    ctx->reset_stage_bytes[stage] = bytes * 2;
-  }
-  int* h_ints = static_cast<int*>(ctx->reset_stage[stage]);
-  std::memcpy(h_ints, structures.data(), structures.size() * sizeof(StructureResetDev));
-  std::memcpy(h_ints + off_entries, entries.data(), entries.size() * sizeof(StructureLinkResetDev));
-  if (n_region) std::memcpy(h_ints + off_region, region_ids.data(), n_region * 4);
-  for (size_t k = 0; k < n_render; ++k) {
-    h_ints[off_render + k] = renderer_ids[k];
-    h_ints[off_pairs + 2 * k] = renderer_ids[k];
-    h_ints[off_pairs + 2 * k + 1] = -1;
-  }
-  std::memcpy(static_cast<uint8_t*>(ctx->reset_stage[stage]) + off_poses, body2world_poses, n_poses * 64);
-  void* dev = nullptr;
-  HIPCHK(hipHostGetDevicePointer(&dev, ctx->reset_stage[stage], 0));
-  const int* d_ints = static_cast<const int*>(dev);
+  const int n_region = int(reads.region_ids.size());
+  const m3t_args::ResetStructuresArgs args(structures.size(), entries.size(), reads.region_ids.size(),
+                                           reads.renderer_ids.size(), pose_body.size());
+  void *host = nullptr, *dev = nullptr;
+  int slot = 0;
+  HIPCHK(ctx->reset_args.Acquire(args.bytes, &host, &dev, &slot));
+  m3t_args::PutInts(host, args.structures, structures.data());
+  m3t_args::PutInts(host, args.links, entries.data());
+  m3t_args::PutInts(host, args.region_ids, reads.region_ids.data());
+  m3t_args::PutRenderers(host, args.renderer_ids, args.renderer_pairs, reads.renderer_ids.data());
+  m3t_args::PutPoses(host, args.poses, body2world_poses);
+  const int* d_region_ids = args.region_ids.in<int>(dev);
   hipLaunchKernelGGL(reset_structures_kernel, dim3(unsigned(structures.size())), dim3(64), 0, ctx->stream,
                      ctx->tree_mode ? ctx->d_treeopts.as<TreeOptDev>() : (const TreeOptDev*)nullptr, ctx->d_poses.as<float>(),
-                     reinterpret_cast<const StructureResetDev*>(d_ints),
-                     reinterpret_cast<const StructureLinkResetDev*>(d_ints + off_entries),
-                     reinterpret_cast<const float*>(static_cast<const uint8_t*>(dev) + off_poses),
-                     ctx->d_region.as<RegionModDev>(), d_ints + off_region, int(n_region), iteration);
+                     args.structures.in<const StructureResetDev>(dev), args.links.in<const StructureLinkResetDev>(dev),
+                     args.poses.in<const float>(dev), ctx->d_region.as<RegionModDev>(), d_region_ids, n_region, iteration);
   // the host mirrors follow: the bodies' poses; the joints stay the device's (PullLinks fetches them when asked)
-  for (size_t k = 0; k < n_poses; ++k)
+  for (size_t k = 0; k < pose_body.size(); ++k)
     std::memcpy(&ctx->body_poses[size_t(pose_body[k]) * 16], body2world_poses + k * 16, 64);
   if (ctx->tree_mode) ctx->links_device_newer = true;
   ctx->roi_end_valid = false;  // the next step's rectangles start from a snapshot of these poses
-  for (int id : region_ids) ctx->region_mods[size_t(id)]->dev.first_iteration = iteration;
-  if (n_render) {
-    int largest = 0;
-    for (int id : renderer_ids) {
-      ctx->renderers[size_t(id)]->rendered = true;
-      largest = std::max(largest, ctx->renderers[size_t(id)]->image_size);
-    }
-    if ((r = LaunchRenderers(ctx, d_ints + off_render, int(n_render), d_ints + off_pairs, int(n_render), largest))) return r;
-  }
+  for (int id : reads.region_ids) ctx->region_mods[size_t(id)]->dev.first_iteration = iteration;
+  if ((r = LaunchStartRenderers(ctx, reads.renderer_ids, args.renderer_ids.in<int>(dev), args.renderer_pairs.in<int>(dev))))
+    return r;
   if (n_region) {
     ScopedKernelTimer timer(ctx, 1);
     hipLaunchKernelGGL(structures_histogram_list_kernel, dim3(unsigned(n_region)), dim3(M3T_BLOCK_THREADS), ctx->lds_hist,
-                       ctx->stream, ctx->d_region.as<RegionModDev>(), d_ints + off_region, ctx->cams_active,
+                       ctx->stream, ctx->d_region.as<RegionModDev>(), d_region_ids, ctx->cams_active,
                        ctx->d_poses.as<float>(), ctx->hist_counts_in_lds ? 1 : 0);
-    for (int id : shared_ids)  // InitializeHistograms of the shared objects these modalities added their samples to (tracker.cpp:441-443)
+    for (int id : reads.shared_ids)  // InitializeHistograms of the shared objects these modalities added their samples to (tracker.cpp:441-443)
       hipLaunchKernelGGL(shared_histogram_finish_kernel, dim3(1), dim3(M3T_BLOCK_THREADS), 0, ctx->stream,
                          ctx->d_shared_histograms.as<SharedHistogramsDev>() + id, 1);
   }
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(ctx->reset_stage_done[stage], ctx->stream));
-  if (ctx->async_ingest) {  // a later asynchronous upload into a slot these launches read waits for them
-    HIPCHK(hipEventRecord(ctx->step_done[ctx->step_counter % Ctx::kStepEvents], ctx->stream));
-    for (int c : cameras) ctx->cameras[c]->last_read_step[ctx->cameras[c]->current] = ctx->step_counter;
-    ++ctx->step_counter;
-  }
-  return M3T_OK;
+  return EndEnqueued(ctx, &ctx->reset_args, slot, &reads.cameras);
 }
 // ---- the evaluators' judgement on the device (m3t_judge.hip) ---------------------------------------------------------
 }  // extern "C"
@@ -4118,13 +4105,9 @@ int m3t_hip_judge_create(m3t_hip_context* ctx, const int* body_ids, int n_bodies
           "judge_create: needs body ids, at least one body and one row");
   REQUIRE(size_t(n_bodies) * size_t(n_rows_max) <= (size_t(1) << 23), M3T_ERR_INVALID_ARGUMENT,
           "judge_create: more than 2^23 results (n_bodies x n_rows_max)");
-  const int n_all = int(ctx->body_poses.size() / 16);
-  std::vector<char> listed(size_t(n_all), 0);
-  for (int i = 0; i < n_bodies; ++i) {
-    REQUIRE(body_ids[i] >= 0 && body_ids[i] < n_all, M3T_ERR_INVALID_ARGUMENT, "judge_create: bad body id");
-    REQUIRE(!listed[body_ids[i]], M3T_ERR_INVALID_ARGUMENT, "judge_create: a body id is listed twice");
-    listed[body_ids[i]] = 1;
-  }
+  std::vector<char> listed;
+  int r = CheckListedIds(ctx, "judge_create", body_ids, n_bodies, int(ctx->body_poses.size() / 16), "body", &listed);
+  if (r) return r;
   HIPCHK(hipSetDevice(ctx->device));
   auto j = std::make_unique<Judge>();
   j->body_ids.assign(body_ids, body_ids + n_bodies);
@@ -4138,8 +4121,7 @@ int m3t_hip_judge_create(m3t_hip_context* ctx, const int* body_ids, int n_bodies
   HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&j->rows_host), bytes, hipHostMallocMapped));
   std::memset(j->rows_host, 0, bytes);
   HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&j->rows_dev), j->rows_host, 0));
-  int r = BuildJudgeTables(ctx, j.get());
-  if (r) return r;
+  if ((r = BuildJudgeTables(ctx, j.get()))) return r;
   ctx->judges.push_back(std::move(j));
   *judge = int(ctx->judges.size()) - 1;
   return M3T_OK;
@@ -4147,27 +4129,21 @@ int m3t_hip_judge_create(m3t_hip_context* ctx, const int* body_ids, int n_bodies
 int m3t_hip_judge_set_thresholds(m3t_hip_context* ctx, int judge, float translation_error_threshold,
                                  float rotation_error_threshold) {
   CHECK_CTX();
-  REQUIRE(judge >= 0 && judge < int(ctx->judges.size()), M3T_ERR_INVALID_ARGUMENT, "judge_set_thresholds: bad judge id");
-  ctx->judges[size_t(judge)]->thr_t = translation_error_threshold;
-  ctx->judges[size_t(judge)]->thr_r = rotation_error_threshold;
+  Judge* j = GetJudge(ctx, judge, "judge_set_thresholds");
+  if (!j) return M3T_ERR_INVALID_ARGUMENT;
+  j->thr_t = translation_error_threshold;
+  j->thr_r = rotation_error_threshold;
   return M3T_OK;
 }
 int m3t_hip_judge_set_vertices(m3t_hip_context* ctx, int judge, int index, const float* xyz, int n_vertices) {
   CHECK_CTX();
-  REQUIRE(judge >= 0 && judge < int(ctx->judges.size()), M3T_ERR_INVALID_ARGUMENT, "judge_set_vertices: bad judge id");
-  Judge* j = ctx->judges[size_t(judge)].get();
+  Judge* j = GetJudge(ctx, judge, "judge_set_vertices");
+  if (!j) return M3T_ERR_INVALID_ARGUMENT;
   REQUIRE(index >= 0 && index < int(j->body_ids.size()), M3T_ERR_INVALID_ARGUMENT, "judge_set_vertices: bad body index");
   REQUIRE(xyz && n_vertices >= 1 && n_vertices <= (1 << 18), M3T_ERR_INVALID_ARGUMENT,
           "judge_set_vertices: 1 to 2^18 vertices");
   HIPCHK(hipSetDevice(ctx->device));
-  const size_t n_padded = (size_t(n_vertices) + 3) / 4 * 4;
-  std::vector<float> padded(n_padded * 4, 0.0f);
-  for (size_t i = 0; i < n_padded; ++i) {
-    const float* v = xyz + 3 * (i < size_t(n_vertices) ? i : 0);  // a copy of vertex 0 never changes a minimum
-    padded[4 * i] = v[0];
-    padded[4 * i + 1] = v[1];
-    padded[4 * i + 2] = v[2];
-  }
+  const std::vector<float> padded = PadVertices(xyz, n_vertices, 4);
   HIPCHK(hipStreamSynchronize(ctx->stream));  // earlier calls may still search the old vertices
   auto mem = std::make_unique<DevMem>();
   HIPCHK(mem->alloc(padded.size() * 4));
@@ -4180,27 +4156,31 @@ int m3t_hip_judge_set_vertices(m3t_hip_context* ctx, int judge, int index, const
 // reset_iteration >= 0, ResetBody of those the device finds lost -- enqueued behind whatever the stream holds (m3t_hip.h).
 int m3t_hip_judge_bodies(m3t_hip_context* ctx, int judge, const float* gt_body2world_poses, int reset_iteration, int* row) {
   CHECK_CTX();
-  REQUIRE(judge >= 0 && judge < int(ctx->judges.size()), M3T_ERR_INVALID_ARGUMENT, "judge_bodies: bad judge id");
-  Judge* j = ctx->judges[size_t(judge)].get();
+  Judge* j = GetJudge(ctx, judge, "judge_bodies");
+  if (!j) return M3T_ERR_INVALID_ARGUMENT;
   REQUIRE(gt_body2world_poses, M3T_ERR_INVALID_ARGUMENT, "judge_bodies: null ground-truth poses");
   REQUIRE(j->n_rows < j->n_rows_max, M3T_ERR_INVALID_ARGUMENT,
           "judge_bodies: the row table is full (judge_read, then judge_clear)");
   const int n = int(j->body_ids.size());
-  const int n_all = int(ctx->body_poses.size() / 16);
   const bool reset = reset_iteration >= 0;
-  std::vector<int> region_ids, region_body_index, region_first(size_t(n) + 1, 0), cameras;
+  int r = M3T_OK;
+  BodiesRead reads;
+  std::vector<int> region_ids, region_body_index, region_first(size_t(n) + 1, 0);  // the modalities grouped by listed body
   if (reset) {  // the host cannot follow a reset the device decides: only what needs no host mirror
-    std::vector<int> index_of(size_t(n_all), -1);
-    for (int i = 0; i < n; ++i) index_of[size_t(j->body_ids[size_t(i)])] = i;
+    std::vector<int> index_of(ctx->body_poses.size() / 16, -1);
+    std::vector<char> listed(index_of.size(), 0);  // (the same as a mask: what CollectReads takes)
+    for (int i = 0; i < n; ++i) {
+      index_of[size_t(j->body_ids[size_t(i)])] = i;
+      listed[size_t(j->body_ids[size_t(i)])] = 1;
+    }
     for (auto& l : ctx->links)
-      REQUIRE(l.body < 0 || index_of[size_t(l.body)] < 0 || (l.parent < 0 && l.children.empty()), M3T_ERR_UNSUPPORTED,
+      REQUIRE(l.body < 0 || !listed[size_t(l.body)] || (l.parent < 0 && l.children.empty()), M3T_ERR_UNSUPPORTED,
               "judge_bodies: a listed body belongs to a structure of more than one link (judge with "
               "reset_iteration < 0 and reset the structure from the host)");
+    reads = CollectReads(ctx, listed);
     std::vector<std::vector<int>> of_body(static_cast<size_t>(n));
-    for (size_t i = 0; i < ctx->region_mods.size(); ++i) {
-      const RegionMod& m = *ctx->region_mods[i];
-      const int li = index_of[size_t(m.body)];
-      if (li < 0) continue;
+    for (int id : reads.region_ids) {
+      const RegionMod& m = *ctx->region_mods[size_t(id)];
       REQUIRE(m.shared_histograms < 0, M3T_ERR_UNSUPPORTED,
               "judge_bodies: a region modality of a listed body uses shared ColorHistograms (call start_modalities)");
       REQUIRE(m.dev.first_iteration == reset_iteration, M3T_ERR_INVALID_ARGUMENT,
@@ -4210,16 +4190,9 @@ int m3t_hip_judge_bodies(m3t_hip_context* ctx, int judge, const float* gt_body2w
               M3T_ERR_UNSUPPORTED,
               "judge_bodies: a region modality of a listed body reads a start-modality renderer (judge with "
               "reset_iteration < 0 and call reset_bodies)");
-      of_body[size_t(li)].push_back(int(i));
-      cameras.push_back(m.camera);
-      if (m.depth_camera >= 0) cameras.push_back(m.depth_camera);
+      of_body[size_t(index_of[size_t(m.body)])].push_back(id);
     }
-    for (auto& m : ctx->depth_mods)
-      if (index_of[size_t(m->body)] >= 0) cameras.push_back(m->camera);
-    for (int c : cameras)
-      REQUIRE(!ctx->cameras[c]->slot_is_roi[ctx->cameras[c]->current], M3T_ERR_UNSUPPORTED,
-              "judge_bodies: a frame slot the modalities read holds the trackers' rectangle only (ROI ingest); "
-              "upload the whole frame into it first (camera_upload_slot)");
+    if ((r = RefuseRoiFrames(ctx, reads.cameras, "judge_bodies"))) return r;
     for (int i = 0; i < n; ++i) {
       for (int id : of_body[size_t(i)]) {
         region_ids.push_back(id);
@@ -4228,41 +4201,19 @@ int m3t_hip_judge_bodies(m3t_hip_context* ctx, int judge, const float* gt_body2w
       region_first[size_t(i) + 1] = int(region_ids.size());
     }
   }
-  HIPCHK(hipSetDevice(ctx->device));
-  const bool untracked_before = ctx->untracked_launches;
-  if (reset && ctx->poses_dirty_host) ctx->roi_end_valid = false;
-  int r = Prepare(ctx, reset);  // (tables and poses that were waiting for their upload anyway)
-  if (r) return r;
-  ctx->untracked_launches = untracked_before;  // reads poses only, or is tracked by a step_done event below
-  // the call's arguments: [ground-truth poses][region modality ids][their listed body][first region of each body]
+  if ((r = BeginEnqueued(ctx, reset))) return r;
   const size_t n_region = region_ids.size();
-  const size_t off_ints = size_t(n) * 64;
-  const size_t bytes = off_ints + (2 * n_region + size_t(n) + 1) * 4;
-  const int stage = j->stage_next;
-  j->stage_next = (stage + 1) % Judge::kStage;
-  if (!j->stage_done[stage]) HIPCHK(hipEventCreateWithFlags(&j->stage_done[stage], hipEventDisableTiming));
-  HIPCHK(hipEventSynchronize(j->stage_done[stage]));  // the call four judgements ago: normally long complete
-  if (j->stage_bytes[stage] < bytes) {
-    if (j->stage[stage]) HIPCHK(hipHostFree(j->stage[stage]));
-    j->stage[stage] = nullptr;
-    j->stage_bytes[stage] = 0;
-    HIPCHK(hipHostMalloc(&j->stage[stage], bytes * 2, hipHostMallocMapped));
-    j->stage_bytes[stage] = bytes * 2;
-  }
-  uint8_t* h = static_cast<uint8_t*>(j->stage[stage]);
-  std::memcpy(h, gt_body2world_poses, size_t(n) * 64);
-  int* h_ints = reinterpret_cast<int*>(h + off_ints);
-  if (n_region) {
-    std::memcpy(h_ints, region_ids.data(), n_region * 4);
-    std::memcpy(h_ints + n_region, region_body_index.data(), n_region * 4);
-  }
-  std::memcpy(h_ints + 2 * n_region, region_first.data(), (size_t(n) + 1) * 4);
-  void* dev = nullptr;
-  HIPCHK(hipHostGetDevicePointer(&dev, j->stage[stage], 0));
-  const float* d_gt = static_cast<const float*>(dev);
-  const int* d_region_ids = reinterpret_cast<const int*>(static_cast<const uint8_t*>(dev) + off_ints);
-  const int* d_region_body = d_region_ids + n_region;
-  const int* d_region_first = d_region_ids + 2 * n_region;
+  const m3t_args::JudgeBodiesArgs args(size_t(n), n_region);
+  void *host = nullptr, *dev = nullptr;
+  int slot = 0;
+  HIPCHK(j->args.Acquire(args.bytes, &host, &dev, &slot));
+  m3t_args::PutPoses(host, args.gt_poses, gt_body2world_poses);
+  m3t_args::PutInts(host, args.region_ids, region_ids.data());
+  m3t_args::PutInts(host, args.region_body, region_body_index.data());
+  m3t_args::PutInts(host, args.region_first, region_first.data());
+  const float* d_gt = args.gt_poses.in<float>(dev);
+  const int *d_region_ids = args.region_ids.in<int>(dev), *d_region_body = args.region_body.in<int>(dev),
+            *d_region_first = args.region_first.in<int>(dev);
   const int row_index = j->n_rows;
   m3t_body_judgement* d_row = j->rows_dev + size_t(row_index) * size_t(n);
   if (!j->row_done[size_t(row_index)])
@@ -4302,25 +4253,17 @@ int m3t_hip_judge_bodies(m3t_hip_context* ctx, int judge, const float* gt_body2w
                        j->d_structure_thresholds.as<float>(), j->n_structures,
                        j->structure_rows_dev + size_t(row_index) * size_t(j->n_structures));
   }
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(j->stage_done[stage], ctx->stream));
+  if ((r = EndEnqueued(ctx, &j->args, slot, reset ? &reads.cameras : nullptr))) return r;
   HIPCHK(hipEventRecord(j->row_done[size_t(row_index)], ctx->stream));
-  if (reset) {
-    ctx->roi_end_valid = false;  // the host's mirror does not vouch for these bodies' poses any more
-    if (ctx->async_ingest) {  // a later asynchronous upload into a slot these launches read waits for them
-      HIPCHK(hipEventRecord(ctx->step_done[ctx->step_counter % Ctx::kStepEvents], ctx->stream));
-      for (int c : cameras) ctx->cameras[c]->last_read_step[ctx->cameras[c]->current] = ctx->step_counter;
-      ++ctx->step_counter;
-    }
-  }
+  if (reset) ctx->roi_end_valid = false;  // the host's mirror does not vouch for these bodies' poses any more
   ++j->n_rows;
   if (row) *row = row_index;
   return M3T_OK;
 }
 int m3t_hip_judge_read(m3t_hip_context* ctx, int judge, int first_row, int n_rows, m3t_body_judgement* out) {
   CHECK_CTX();
-  REQUIRE(judge >= 0 && judge < int(ctx->judges.size()), M3T_ERR_INVALID_ARGUMENT, "judge_read: bad judge id");
-  Judge* j = ctx->judges[size_t(judge)].get();
+  Judge* j = GetJudge(ctx, judge, "judge_read");
+  if (!j) return M3T_ERR_INVALID_ARGUMENT;
   REQUIRE(first_row >= 0 && n_rows >= 0 && first_row <= j->n_rows && n_rows <= j->n_rows - first_row,
           M3T_ERR_INVALID_ARGUMENT, "judge_read: rows that have not been judged");
   if (n_rows == 0) return M3T_OK;
@@ -4339,8 +4282,8 @@ int m3t_hip_judge_set_structures(m3t_hip_context* ctx, int judge, int n_structur
                                  const int* group_first_index, const int* listed_body_indices,
                                  const float* error_thresholds) {
   CHECK_CTX();
-  REQUIRE(judge >= 0 && judge < int(ctx->judges.size()), M3T_ERR_INVALID_ARGUMENT, "judge_set_structures: bad judge id");
-  Judge* j = ctx->judges[size_t(judge)].get();
+  Judge* j = GetJudge(ctx, judge, "judge_set_structures");
+  if (!j) return M3T_ERR_INVALID_ARGUMENT;
   REQUIRE(n_structures >= 1 && structure_first_group && group_first_index && listed_body_indices && error_thresholds,
           M3T_ERR_INVALID_ARGUMENT, "judge_set_structures: needs at least one structure and all four lists");
   REQUIRE(size_t(n_structures) * size_t(j->n_rows_max) <= (size_t(1) << 23), M3T_ERR_INVALID_ARGUMENT,
@@ -4385,8 +4328,8 @@ int m3t_hip_judge_set_structures(m3t_hip_context* ctx, int judge, int n_structur
 }
 int m3t_hip_judge_read_structures(m3t_hip_context* ctx, int judge, int first_row, int n_rows, m3t_structure_judgement* out) {
   CHECK_CTX();
-  REQUIRE(judge >= 0 && judge < int(ctx->judges.size()), M3T_ERR_INVALID_ARGUMENT, "judge_read_structures: bad judge id");
-  Judge* j = ctx->judges[size_t(judge)].get();
+  Judge* j = GetJudge(ctx, judge, "judge_read_structures");
+  if (!j) return M3T_ERR_INVALID_ARGUMENT;
   REQUIRE(j->n_structures > 0, M3T_ERR_INVALID_ARGUMENT, "judge_read_structures: judge_set_structures first");
   REQUIRE(first_row >= 0 && n_rows >= 0 && first_row <= j->n_rows && n_rows <= j->n_rows - first_row,
           M3T_ERR_INVALID_ARGUMENT, "judge_read_structures: rows that have not been judged");
@@ -4402,8 +4345,8 @@ int m3t_hip_judge_read_structures(m3t_hip_context* ctx, int judge, int first_row
 // outside the frame loop, like judge_set_vertices.
 int m3t_hip_judge_set_add_only(m3t_hip_context* ctx, int judge, int index, const float* geometry2body_pose) {
   CHECK_CTX();
-  REQUIRE(judge >= 0 && judge < int(ctx->judges.size()), M3T_ERR_INVALID_ARGUMENT, "judge_set_add_only: bad judge id");
-  Judge* j = ctx->judges[size_t(judge)].get();
+  Judge* j = GetJudge(ctx, judge, "judge_set_add_only");
+  if (!j) return M3T_ERR_INVALID_ARGUMENT;
   REQUIRE(index >= 0 && index < int(j->body_ids.size()), M3T_ERR_INVALID_ARGUMENT, "judge_set_add_only: bad body index");
   REQUIRE(j->n_rows == 0, M3T_ERR_INVALID_ARGUMENT, "judge_set_add_only: rows have been judged already (judge_clear first)");
   std::array<float, 12> g = {1.0f, 0.0f, 0.0f, 0.0f, 1.0f, 0.0f, 0.0f, 0.0f, 1.0f, 0.0f, 0.0f, 0.0f};
@@ -4433,14 +4376,7 @@ int m3t_hip_vertices_diameter(m3t_hip_context* ctx, const float* xyz, int n_vert
   }
   HIPCHK(hipSetDevice(ctx->device));
   const size_t n_tiles = (size_t(n_vertices) + M3T_DIAMETER_TILE - 1) / M3T_DIAMETER_TILE;
-  const size_t n_padded = n_tiles * M3T_DIAMETER_TILE;
-  std::vector<float> padded(n_padded * 4, 0.0f);
-  for (size_t i = 0; i < n_padded; ++i) {
-    const float* v = xyz + 3 * (i < size_t(n_vertices) ? i : 0);  // a copy of vertex 0 forms pairs of the set only
-    padded[4 * i] = v[0];
-    padded[4 * i + 1] = v[1];
-    padded[4 * i + 2] = v[2];
-  }
+  const std::vector<float> padded = PadVertices(xyz, n_vertices, M3T_DIAMETER_TILE);
   HIPCHK(hipStreamSynchronize(ctx->stream));
   DevMem vertices, max_bits;
   HIPCHK(vertices.alloc(padded.size() * 4));
@@ -4462,8 +4398,9 @@ int m3t_hip_vertices_diameter(m3t_hip_context* ctx, const float* xyz, int n_vert
 }
 int m3t_hip_judge_clear(m3t_hip_context* ctx, int judge) {
   CHECK_CTX();
-  REQUIRE(judge >= 0 && judge < int(ctx->judges.size()), M3T_ERR_INVALID_ARGUMENT, "judge_clear: bad judge id");
-  ctx->judges[size_t(judge)]->n_rows = 0;
+  Judge* j = GetJudge(ctx, judge, "judge_clear");
+  if (!j) return M3T_ERR_INVALID_ARGUMENT;
+  j->n_rows = 0;
   return M3T_OK;
 }
 int m3t_hip_calculate_correspondences(m3t_hip_context* ctx, int iteration, int corr_iteration) {
