@@ -359,6 +359,8 @@ _HIP_ONLY = {
     "judge_set_structures": [C.c_int, C.c_int, c_int_p, c_int_p, c_int_p, c_float_p],
     "judge_read_structures": [C.c_int, C.c_int, C.c_int, C.c_void_p],
     "judge_set_add_only": [C.c_int, C.c_int, c_float_p],
+    "judge_set_reset_renderers": [C.c_int, C.c_int],
+    "judge_set_reset_target": [C.c_int, C.c_int, C.c_int],
     "vertices_diameter": [c_float_p, C.c_int, c_float_p],
 }
 

@@ -69,4 +69,14 @@ struct JudgeBodiesArgs : Layout {
       : gt_poses(Poses(n)), region_ids(Ints(n_region)), region_body(Ints(n_region)), region_first(Ints(n + 1)) {}
 };
 
+// judge_bodies of a judge that may run start-modality renderers (m3t_hip_judge_set_reset_renderers): the four lists of
+// JudgeBodiesArgs where JudgeBodiesArgs puts them, then [{renderer, twin or -1} pairs][first reader of each pair,
+// n_pairs + 1][readers: indices into the judge's list]
+struct JudgeBodiesRenderArgs : Layout {
+  Segment gt_poses, region_ids, region_body, region_first, renderer_pairs, reader_first, readers;
+  JudgeBodiesRenderArgs(size_t n, size_t n_region, size_t n_pairs, size_t n_readers)
+      : gt_poses(Poses(n)), region_ids(Ints(n_region)), region_body(Ints(n_region)), region_first(Ints(n + 1)),
+        renderer_pairs(Ints(2 * n_pairs)), reader_first(Ints(n_pairs + 1)), readers(Ints(n_readers)) {}
+};
+
 }  // namespace m3t_args

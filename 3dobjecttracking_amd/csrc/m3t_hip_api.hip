@@ -239,6 +239,10 @@ struct Judge {  // m3t_hip_judge_*: the evaluators' judgement of a list of bodie
   int n_structures = 0;
   DevMem d_structure_ints, d_structure_thresholds;  // [first group of each structure | first index of each group | indices]
   size_t structure_groups = 0;
+  // m3t_hip_judge_set_reset_target: per listed body the body a reset writes (-1: the listed body itself);
+  // m3t_hip_judge_set_reset_renderers: a resetting call may run start-modality renderers, decided on the device
+  std::vector<int> targets;
+  bool reset_renderers = false;
   m3t_structure_judgement* structure_rows_host = nullptr;  // [n_rows_max][n_structures], written by the kernel in place
   m3t_structure_judgement* structure_rows_dev = nullptr;
   ~Judge() {
@@ -273,6 +277,7 @@ struct m3t_hip_context {
   int n_render_region_pairs = 0, n_render_all_pairs = 0;
   int n_render_region = 0, n_render_all = 0;
   int lds_raster = -1;  // focused_resolve_kernel (z-buffer in LDS) usable on this device: -1 not tried yet
+  int judge_render_always = -1;  // M3T_HIP_JUDGE_RENDER_ALWAYS (developer switch, tools/occlusion_judge_timing.py): -1 not read yet
   std::vector<Link> links;
   std::vector<ConstraintH> constraints;
   std::vector<SoftConstraintH> soft_constraints;
@@ -1074,6 +1079,31 @@ int UploadTreeTables(Ctx* ctx) {
   return M3T_OK;
 }
 
+// A list of renderers as {renderer, twin or -1} pairs.  Twins: two renderers of a list that differ in nothing but the id
+// written (focused_setup_kernel) are drawn once.
+std::vector<int> RendererPairs(Ctx* ctx, const std::vector<int>& list) {
+  auto same_rendering = [&](int a, int b) {
+    const RendererH& x = *ctx->renderers[a];
+    const RendererH& y = *ctx->renderers[b];
+    return x.camera == y.camera && x.geometry == y.geometry && x.image_size == y.image_size && x.z_min == y.z_min &&
+           x.z_max == y.z_max && x.referenced == y.referenced;
+  };
+  std::vector<int> pairs;
+  std::vector<char> taken(list.size(), 0);
+  for (size_t i = 0; i < list.size(); ++i) {
+    if (taken[i]) continue;
+    int twin = -1;
+    for (size_t j = i + 1; j < list.size() && twin < 0; ++j)
+      if (!taken[j] && same_rendering(list[i], list[j])) {
+        twin = list[j];
+        taken[j] = 1;
+      }
+    pairs.push_back(list[i]);
+    pairs.push_back(twin);
+  }
+  return pairs;
+}
+
 // RendererDev table + the renderer fields of the modality tables + the two "which renderers" lists
 // (region modalities' renderers for start / results, all referenced ones for correspondences)
 int UploadRendererTables(Ctx* ctx) {
@@ -1172,30 +1202,7 @@ int UploadRendererTables(Ctx* ctx) {
     if (for_region[i]) list_region.push_back(int(i));
     if (for_all[i]) list_all.push_back(int(i));
   }
-  // twins: two renderers of a list that differ in nothing but the id written (focused_setup_kernel) are drawn once
-  auto same_rendering = [&](int a, int b) {
-    const RendererH& x = *ctx->renderers[a];
-    const RendererH& y = *ctx->renderers[b];
-    return x.camera == y.camera && x.geometry == y.geometry && x.image_size == y.image_size && x.z_min == y.z_min &&
-           x.z_max == y.z_max && x.referenced == y.referenced;
-  };
-  auto pairs_of = [&](const std::vector<int>& list) {
-    std::vector<int> pairs;
-    std::vector<char> taken(list.size(), 0);
-    for (size_t i = 0; i < list.size(); ++i) {
-      if (taken[i]) continue;
-      int twin = -1;
-      for (size_t j = i + 1; j < list.size() && twin < 0; ++j)
-        if (!taken[j] && same_rendering(list[i], list[j])) {
-          twin = list[j];
-          taken[j] = 1;
-        }
-      pairs.push_back(list[i]);
-      pairs.push_back(twin);
-    }
-    return pairs;
-  };
-  const std::vector<int> pairs_region = pairs_of(list_region), pairs_all = pairs_of(list_all);
+  const std::vector<int> pairs_region = RendererPairs(ctx, list_region), pairs_all = RendererPairs(ctx, list_all);
   ctx->n_render_region_pairs = int(pairs_region.size() / 2);
   ctx->n_render_all_pairs = int(pairs_all.size() / 2);
   HIPCHK(ctx->d_render_region_pairs.alloc(std::max<size_t>(1, pairs_region.size()) * 4));
@@ -1218,8 +1225,11 @@ int UploadRendererTables(Ctx* ctx) {
 // Renderings whose z-buffer fits the LDS of a CU: set-up + survivor list (32 slices of the triangle lists per renderer),
 // then one workgroup per renderer that rasterises the survivors in LDS and writes the images.  Larger ones: clear + crop,
 // rasterise into a z-buffer in memory, unpack.
-int LaunchRenderers(Ctx* ctx, const int* which, int n_which, const int* pairs, int n_pairs, int largest_image_size) {
-  if (n_which == 0) return M3T_OK;
+struct RenderLaunchShape {
+  int slices, bands;
+  size_t lds;  // of a resolve workgroup
+};
+RenderLaunchShape RenderShape(int n_pairs, int largest_image_size) {
   // work spread: ~128 set-up workgroups (slices of the triangle lists) and ~256 resolve workgroups (bands of image
   // rows, at least two rows each) per launch, whatever the number of renderings (measured on the reference's test
   // scene, two pairs of twins, renderer-fed step: 32 bands 0.633 ms, 64: 0.624, 100: 0.611; 64 -> 128 slices: no
@@ -1228,25 +1238,37 @@ int LaunchRenderers(Ctx* ctx, const int* which, int n_which, const int* pairs, i
   // VGPRs, one per CU at a time, each paying the projection and the matrix chain for two trips over its triangles:
   // 131 us per set-up launch; 2 slices per pair = one workgroup per CU: 2.33 -> 1.64 ms per step,
   // profiles/r05_render64_knobs.txt)
-  int slices = std::min(128, std::max(2, 128 / std::max(1, n_pairs)));
-  int bands = std::min(std::max(8, largest_image_size / 2), std::max(8, 256 / std::max(1, n_pairs)));
-  if (const char* e = std::getenv("M3T_HIP_RASTER_BANDS")) bands = std::max(1, std::atoi(e));    // developer overrides
-  if (const char* e = std::getenv("M3T_HIP_RASTER_SLICES")) slices = std::max(1, std::atoi(e));
-  const size_t band_rows = (size_t(largest_image_size) + bands - 1) / bands;
-  const size_t lds = band_rows * largest_image_size * 4 + (M3T_BLOCK_THREADS + 1 + 16 + 4 * M3T_BLOCK_THREADS) * 4;  // z-buffer band | prefix sums | wave totals | per-thread counts
+  RenderLaunchShape s;
+  s.slices = std::min(128, std::max(2, 128 / std::max(1, n_pairs)));
+  s.bands = std::min(std::max(8, largest_image_size / 2), std::max(8, 256 / std::max(1, n_pairs)));
+  if (const char* e = std::getenv("M3T_HIP_RASTER_BANDS")) s.bands = std::max(1, std::atoi(e));    // developer overrides
+  if (const char* e = std::getenv("M3T_HIP_RASTER_SLICES")) s.slices = std::max(1, std::atoi(e));
+  const size_t band_rows = (size_t(largest_image_size) + s.bands - 1) / s.bands;
+  s.lds = band_rows * largest_image_size * 4 + (M3T_BLOCK_THREADS + 1 + 16 + 4 * M3T_BLOCK_THREADS) * 4;  // z-buffer band | prefix sums | wave totals | per-thread counts
+  return s;
+}
+// the two-launch form (z-buffer band in LDS) for a rendering of this shape?
+bool LdsRasterFits(Ctx* ctx, const RenderLaunchShape& shape, int largest_image_size) {
   if (ctx->lds_raster < 0) {  // once per context (= per device)
     ctx->lds_raster = 1;
     if (std::getenv("M3T_HIP_NO_LDS_RASTER")) ctx->lds_raster = 0;
-    else if (hipFuncSetAttribute(reinterpret_cast<const void*>(focused_resolve_kernel),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-      (void)hipGetLastError();
-      ctx->lds_raster = 0;
-    }
+    else
+      for (const void* kernel : {reinterpret_cast<const void*>(focused_resolve_kernel),
+                                 reinterpret_cast<const void*>(focused_resolve_flagged_kernel)})
+        if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
+          (void)hipGetLastError();
+          ctx->lds_raster = 0;
+        }
   }
-  if (ctx->lds_raster == 1 && largest_image_size > 0 && lds <= size_t(160) * 1024) {
-    hipLaunchKernelGGL(focused_setup_kernel, dim3(slices, n_pairs), dim3(M3T_BLOCK_THREADS), 0, ctx->stream,
+  return ctx->lds_raster == 1 && largest_image_size > 0 && shape.lds <= size_t(160) * 1024;
+}
+int LaunchRenderers(Ctx* ctx, const int* which, int n_which, const int* pairs, int n_pairs, int largest_image_size) {
+  if (n_which == 0) return M3T_OK;
+  const RenderLaunchShape shape = RenderShape(n_pairs, largest_image_size);
+  if (LdsRasterFits(ctx, shape, largest_image_size)) {
+    hipLaunchKernelGGL(focused_setup_kernel, dim3(shape.slices, n_pairs), dim3(M3T_BLOCK_THREADS), 0, ctx->stream,
                        ctx->d_renderers.as<RendererDev>(), pairs, ctx->cams_active, ctx->d_poses.as<float>());
-    hipLaunchKernelGGL(focused_resolve_kernel, dim3(n_pairs, bands), dim3(M3T_BLOCK_THREADS), lds, ctx->stream,
+    hipLaunchKernelGGL(focused_resolve_kernel, dim3(n_pairs, shape.bands), dim3(M3T_BLOCK_THREADS), shape.lds, ctx->stream,
                        ctx->d_renderers.as<RendererDev>(), pairs);
     HIPCHK(hipGetLastError());
     return M3T_OK;
@@ -4054,6 +4076,7 @@ int BuildJudgeTables(Ctx* ctx, Judge* j) {
     JudgeBodyDev& b = bodies[size_t(i)];
     b.vertices = j->vertices[size_t(i)] ? j->vertices[size_t(i)]->as<float4>() : nullptr;
     b.body = j->body_ids[size_t(i)];
+    b.target = j->targets[size_t(i)] >= 0 ? j->targets[size_t(i)] : b.body;
     b.n_vertices = j->n_vertices[size_t(i)];
     b.first_part = int(parts.size());
     if (j->add_only[size_t(i)]) {  // no workgroup of judge_bodies_kernel, nothing for judge_finish_kernel
@@ -4062,6 +4085,7 @@ int BuildJudgeTables(Ctx* ctx, Judge* j) {
       a.vertices = b.vertices;
       a.index = i;
       a.body = b.body;
+      a.target = b.target;
       a.n_vertices = b.n_vertices;
       a.first_part = int(add_parts.size());
       a.n_parts = std::max(1, (a.n_vertices + M3T_JUDGE_ADD_SPLIT - 1) / M3T_JUDGE_ADD_SPLIT);
@@ -4115,6 +4139,7 @@ int m3t_hip_judge_create(m3t_hip_context* ctx, const int* body_ids, int n_bodies
   j->n_vertices.assign(size_t(n_bodies), 0);
   j->vertices.resize(size_t(n_bodies));
   j->add_only.assign(size_t(n_bodies), 0);
+  j->targets.assign(size_t(n_bodies), -1);
   j->geometry2body.resize(size_t(n_bodies));
   j->row_done.assign(size_t(n_rows_max), nullptr);
   const size_t bytes = size_t(n_bodies) * size_t(n_rows_max) * sizeof(m3t_body_judgement);
@@ -4166,12 +4191,19 @@ int m3t_hip_judge_bodies(m3t_hip_context* ctx, int judge, const float* gt_body2w
   int r = M3T_OK;
   BodiesRead reads;
   std::vector<int> region_ids, region_body_index, region_first(size_t(n) + 1, 0);  // the modalities grouped by listed body
+  std::vector<int> render_pairs, reader_first, readers;  // judge_set_reset_renderers: what the device may render, and for whom
+  RenderLaunchShape render_shape{};
+  if (ctx->judge_render_always < 0)  // once per context, like the other developer knobs
+    ctx->judge_render_always = std::getenv("M3T_HIP_JUDGE_RENDER_ALWAYS") ? 1 : 0;
+  const bool render_always = ctx->judge_render_always == 1;  // every pair is rendered, lost reader or not
   if (reset) {  // the host cannot follow a reset the device decides: only what needs no host mirror
+    // (the bodies a reset writes -- the reset targets, by default the listed bodies themselves -- are "listed" below)
     std::vector<int> index_of(ctx->body_poses.size() / 16, -1);
     std::vector<char> listed(index_of.size(), 0);  // (the same as a mask: what CollectReads takes)
     for (int i = 0; i < n; ++i) {
-      index_of[size_t(j->body_ids[size_t(i)])] = i;
-      listed[size_t(j->body_ids[size_t(i)])] = 1;
+      const int written = j->targets[size_t(i)] >= 0 ? j->targets[size_t(i)] : j->body_ids[size_t(i)];
+      index_of[size_t(written)] = i;
+      listed[size_t(written)] = 1;
     }
     for (auto& l : ctx->links)
       REQUIRE(l.body < 0 || !listed[size_t(l.body)] || (l.parent < 0 && l.children.empty()), M3T_ERR_UNSUPPORTED,
@@ -4186,7 +4218,8 @@ int m3t_hip_judge_bodies(m3t_hip_context* ctx, int judge, const float* gt_body2w
       REQUIRE(m.dev.first_iteration == reset_iteration, M3T_ERR_INVALID_ARGUMENT,
               "judge_bodies: first_iteration of a listed body's region modality differs from reset_iteration (the "
               "host could not follow a change the device decides; start_modalities(reset_iteration) first)");
-      REQUIRE(!(m.dev.model_occlusions && m.depth_renderer >= 0) && !(m.dev.use_region_checking && m.silhouette_renderer >= 0),
+      REQUIRE(j->reset_renderers ||
+                  (!(m.dev.model_occlusions && m.depth_renderer >= 0) && !(m.dev.use_region_checking && m.silhouette_renderer >= 0)),
               M3T_ERR_UNSUPPORTED,
               "judge_bodies: a region modality of a listed body reads a start-modality renderer (judge with "
               "reset_iteration < 0 and call reset_bodies)");
@@ -4200,17 +4233,54 @@ int m3t_hip_judge_bodies(m3t_hip_context* ctx, int judge, const float* gt_body2w
       }
       region_first[size_t(i) + 1] = int(region_ids.size());
     }
+    if (j->reset_renderers && !reads.renderer_ids.empty()) {
+      // the renderers as reset_bodies would list them for ALL the targets, paired with their twins; per pair the
+      // entries of the judge whose target reads one of the two
+      HIPCHK(hipSetDevice(ctx->device));
+      render_pairs = RendererPairs(ctx, reads.renderer_ids);
+      const int n_pairs = int(render_pairs.size() / 2);
+      int largest = 0;
+      for (int id : reads.renderer_ids) largest = std::max(largest, ctx->renderers[size_t(id)]->image_size);
+      render_shape = RenderShape(n_pairs, largest);
+      REQUIRE(LdsRasterFits(ctx, render_shape, largest), M3T_ERR_UNSUPPORTED,
+              "judge_bodies: a start-modality renderer of image size " + std::to_string(largest) +
+                  " needs the three-launch form (its z-buffer band does not fit the LDS, or the LDS form is switched "
+                  "off): a device-decided run covers the two-launch form only (judge with reset_iteration < 0 and call "
+                  "reset_bodies)");
+      reader_first.push_back(0);
+      for (int p = 0; p < n_pairs; ++p) {
+        std::vector<char> reads_pair(static_cast<size_t>(n), 0);
+        for (int id : reads.region_ids) {
+          const RegionMod& m = *ctx->region_mods[size_t(id)];
+          for (int renderer : {m.dev.model_occlusions ? m.depth_renderer : -1, m.dev.use_region_checking ? m.silhouette_renderer : -1})
+            if (renderer >= 0 && (renderer == render_pairs[size_t(2 * p)] || renderer == render_pairs[size_t(2 * p + 1)]))
+              reads_pair[size_t(index_of[size_t(m.body)])] = 1;
+        }
+        for (int i = 0; i < n; ++i)
+          if (reads_pair[size_t(i)]) readers.push_back(i);
+        reader_first.push_back(int(readers.size()));
+      }
+    }
   }
   if ((r = BeginEnqueued(ctx, reset))) return r;
   const size_t n_region = region_ids.size();
-  const m3t_args::JudgeBodiesArgs args(size_t(n), n_region);
+  const size_t n_pairs = render_pairs.size() / 2;
+  // (a judge without judge_set_reset_renderers fills the block of JudgeBodiesArgs, byte for byte as before)
+  const m3t_args::JudgeBodiesRenderArgs render_args(size_t(n), n_region, n_pairs, readers.size());
+  const m3t_args::JudgeBodiesArgs plain_args(size_t(n), n_region);
+  const m3t_args::JudgeBodiesArgs& args = plain_args;
   void *host = nullptr, *dev = nullptr;
   int slot = 0;
-  HIPCHK(j->args.Acquire(args.bytes, &host, &dev, &slot));
+  HIPCHK(j->args.Acquire(n_pairs ? render_args.bytes : plain_args.bytes, &host, &dev, &slot));
   m3t_args::PutPoses(host, args.gt_poses, gt_body2world_poses);
   m3t_args::PutInts(host, args.region_ids, region_ids.data());
   m3t_args::PutInts(host, args.region_body, region_body_index.data());
   m3t_args::PutInts(host, args.region_first, region_first.data());
+  if (n_pairs) {  // behind the four lists, which sit where JudgeBodiesArgs puts them
+    m3t_args::PutInts(host, render_args.renderer_pairs, render_pairs.data());
+    m3t_args::PutInts(host, render_args.reader_first, reader_first.data());
+    m3t_args::PutInts(host, render_args.readers, readers.data());
+  }
   const float* d_gt = args.gt_poses.in<float>(dev);
   const int *d_region_ids = args.region_ids.in<int>(dev), *d_region_body = args.region_body.in<int>(dev),
             *d_region_first = args.region_first.in<int>(dev);
@@ -4239,6 +4309,17 @@ int m3t_hip_judge_bodies(m3t_hip_context* ctx, int judge, const float* gt_body2w
     hipLaunchKernelGGL(judge_finish_kernel, dim3(unsigned(n)), dim3(64), 0, ctx->stream, ctx->d_poses.as<float>(),
                        j->d_bodies.as<JudgeBodyDev>(), d_gt, reset_iteration, ctx->d_region.as<RegionModDev>(),
                        d_region_ids, d_region_first, j->d_flags.as<int>(), d_row, j->d_partial.as<double>());
+  if (n_pairs) {  // the start-modality renderers some lost body reads, with the poses after all of the call's resets
+    const int* d_pairs = render_args.renderer_pairs.in<int>(dev);
+    const int *d_reader_first = render_args.reader_first.in<int>(dev), *d_readers = render_args.readers.in<int>(dev);
+    hipLaunchKernelGGL(focused_setup_flagged_kernel, dim3(unsigned(render_shape.slices), unsigned(n_pairs)),
+                       dim3(M3T_BLOCK_THREADS), 0, ctx->stream, ctx->d_renderers.as<RendererDev>(), d_pairs,
+                       ctx->cams_active, ctx->d_poses.as<float>(), j->d_flags.as<int>(), d_reader_first, d_readers,
+                       render_always ? 1 : 0);
+    hipLaunchKernelGGL(focused_resolve_flagged_kernel, dim3(unsigned(n_pairs), unsigned(render_shape.bands)),
+                       dim3(M3T_BLOCK_THREADS), render_shape.lds, ctx->stream, ctx->d_renderers.as<RendererDev>(), d_pairs,
+                       j->d_flags.as<int>(), d_reader_first, d_readers, render_always ? 1 : 0);
+  }
   if (n_region) {
     ScopedKernelTimer timer(ctx, 1);
     hipLaunchKernelGGL(region_histogram_flagged_kernel, dim3(unsigned(n_region)), dim3(M3T_BLOCK_THREADS), ctx->lds_hist,
@@ -4259,6 +4340,44 @@ int m3t_hip_judge_bodies(m3t_hip_context* ctx, int judge, const float* gt_body2w
   ++j->n_rows;
   if (row) *row = row_index;
   return M3T_OK;
+}
+// A resetting judge_bodies call of this judge may run the start-modality renderers of the bodies it resets, decided on
+// the device (m3t_hip.h).  Off: the call refuses such bodies, as it always did.
+int m3t_hip_judge_set_reset_renderers(m3t_hip_context* ctx, int judge, int enable) {
+  CHECK_CTX();
+  Judge* j = GetJudge(ctx, judge, "judge_set_reset_renderers");
+  if (!j) return M3T_ERR_INVALID_ARGUMENT;
+  j->reset_renderers = enable != 0;
+  return M3T_OK;
+}
+// Entry `index` of the judge resets body_id instead of its listed body when it is found lost (-1: its listed body again;
+// m3t_hip.h).  Waits for the stream and uploads: outside the frame loop, like judge_set_vertices.
+int m3t_hip_judge_set_reset_target(m3t_hip_context* ctx, int judge, int index, int body_id) {
+  CHECK_CTX();
+  Judge* j = GetJudge(ctx, judge, "judge_set_reset_target");
+  if (!j) return M3T_ERR_INVALID_ARGUMENT;
+  const int n = int(j->body_ids.size());
+  REQUIRE(index >= 0 && index < n, M3T_ERR_INVALID_ARGUMENT, "judge_set_reset_target: bad body index");
+  REQUIRE(body_id >= -1 && body_id < int(ctx->body_poses.size() / 16), M3T_ERR_INVALID_ARGUMENT,
+          "judge_set_reset_target: bad body id");
+  REQUIRE(j->n_rows == 0, M3T_ERR_INVALID_ARGUMENT,
+          "judge_set_reset_target: rows have been judged already (judge_clear first)");
+  const int target = body_id == j->body_ids[size_t(index)] ? -1 : body_id;
+  for (int k = 0; k < n && target >= 0; ++k) {
+    if (k == index) continue;
+    // (a listed body is read by its own entry's workgroups while another entry's reset would write it)
+    REQUIRE(j->body_ids[size_t(k)] != target, M3T_ERR_INVALID_ARGUMENT,
+            "judge_set_reset_target: the body is the listed body of another entry of the judge (it would be written by "
+            "two entries, or written by one while the other reads its pose)");
+    REQUIRE(j->targets[size_t(k)] != target, M3T_ERR_INVALID_ARGUMENT,
+            "judge_set_reset_target: the body would be written by two entries of the judge");
+  }
+  HIPCHK(hipSetDevice(ctx->device));
+  const int before = j->targets[size_t(index)];
+  j->targets[size_t(index)] = target;
+  const int r = BuildJudgeTables(ctx, j);
+  if (r) j->targets[size_t(index)] = before;  // (a failed upload: the next upload is of the old table again)
+  return r;
 }
 int m3t_hip_judge_read(m3t_hip_context* ctx, int judge, int first_row, int n_rows, m3t_body_judgement* out) {
   CHECK_CTX();

@@ -17,6 +17,7 @@ struct JudgeBodyDev {        // one listed body
   int body;                  // body id
   int n_vertices;            // 0: pose errors only
   int first_part, n_parts;   // its workgroups in the launch / its rows of the partial sums
+  int target;                // the body a reset writes (m3t_hip_judge_set_reset_target; by default `body`)
 };
 struct JudgePartDev {
   int index, part;           // listed body, query range [part * Q, (part + 1) * Q)
@@ -158,9 +159,10 @@ __device__ __forceinline__ void judge_bodies_body(float* body_poses, const Judge
   } else {
     __syncthreads();
   }
-  // a body in one part: its workgroup is the only reader of the pose (a split body: judge_finish_kernel)
+  // a body in one part: its workgroup is the only reader of the pose (a split body: judge_finish_kernel); a reset
+  // target other than the body is no listed body of the judge: nobody in this launch reads its pose
   if (b.n_parts == 1 && s_reset)
-    judge_reset_body(body_poses, b.body, s_gt, mods, region_ids, region_first[wp.index], region_first[wp.index + 1],
+    judge_reset_body(body_poses, b.target, s_gt, mods, region_ids, region_first[wp.index], region_first[wp.index + 1],
                      reset_iteration);
 }
 
@@ -197,7 +199,7 @@ judge_finish_kernel(float* body_poses, const JudgeBodyDev* bodies, const float* 
     row[blockIdx.x].adds_error = float(adds / double(b.n_vertices));
   }
   if (flags[blockIdx.x])
-    judge_reset_body(body_poses, b.body, gt_poses + 16 * blockIdx.x, mods, region_ids, region_first[blockIdx.x],
+    judge_reset_body(body_poses, b.target, gt_poses + 16 * blockIdx.x, mods, region_ids, region_first[blockIdx.x],
                      region_first[blockIdx.x + 1], reset_iteration);
 }
 

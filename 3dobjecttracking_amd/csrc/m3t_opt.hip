@@ -18,6 +18,7 @@ struct JudgeAddBodyDev {     // one ADD-only body
   int body;                  // body id
   int n_vertices;            // 0: pose errors only
   int first_part, n_parts;   // its workgroups in the launch / its partial sums
+  int target;                // the body a reset writes (JudgeBodyDev::target)
   float geometry2body[12];   // column-major 3 x 4: [c * 3 + r]
 };
 
@@ -141,7 +142,7 @@ judge_add_only_kernel(float* body_poses, const JudgeAddBodyDev* bodies, const Ju
   }
   // a body in one part: its workgroup is the only reader of the pose (a split body: judge_add_only_finish_kernel)
   if (n_parts == 1 && s_reset)
-    judge_reset_body(body_poses, b.body, s_gt, mods, region_ids, region_first[index], region_first[index + 1],
+    judge_reset_body(body_poses, b.target, s_gt, mods, region_ids, region_first[index], region_first[index + 1],
                      reset_iteration);
 }
 
@@ -160,7 +161,7 @@ judge_add_only_finish_kernel(float* body_poses, const JudgeAddBodyDev* bodies, c
     row[index].add_error = float(add / double(b.n_vertices));
   }
   if (flags[index])
-    judge_reset_body(body_poses, b.body, gt_poses + 16 * index, mods, region_ids, region_first[index],
+    judge_reset_body(body_poses, b.target, gt_poses + 16 * index, mods, region_ids, region_first[index],
                      region_first[index + 1], reset_iteration);
 }
 

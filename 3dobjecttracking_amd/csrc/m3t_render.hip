@@ -191,96 +191,11 @@ static_assert(sizeof(RasterSurvivor) == M3T_SURVIVOR_BYTES, "M3T_SURVIVOR_BYTES"
 // depth range and image size (a FocusedBasicDepthRenderer and a FocusedSilhouetteRenderer of one camera, say): its
 // rendering is this one -- the z-buffer word orders by depth and draw order, the id byte follows from the draw order --
 // so one set-up and one rasterisation serve both; the resolve kernel writes the twin's images with the twin's ids.
+// (The two kernels' bodies live in m3t_render_setup.inc / m3t_render_resolve.inc: the flagged kernels below include the
+// same text behind their test, and these two compile to what they always were.)
 __global__ void __launch_bounds__(M3T_BLOCK_THREADS)
 focused_setup_kernel(const RendererDev* renderers, const int* which, const CameraDev* cams, const float* body_poses) {
-  const RendererDev& r = renderers[which[2 * blockIdx.y]];
-  const int twin = which[2 * blockIdx.y + 1];
-  const CameraDev& cam = cams[r.camera];
-  const FocusedProjection f = focused_projection(r, cam, body_poses);
-  if (threadIdx.x == 0 && blockIdx.x == 0) {  // the crop, for the modalities that read the rendering
-    for (int w = 0; w < (twin >= 0 ? 2 : 1); ++w) {
-      float* state = w == 0 ? r.state : renderers[twin].state;
-      state[RS_CORNER_U] = f.corner_u;
-      state[RS_CORNER_V] = f.corner_v;
-      state[RS_SCALE] = f.scale;
-      state[RS_TERM_A] = r.z_max * r.z_min * 65535.0f / (r.z_max - r.z_min);  // renderer.cpp:567-570
-      state[RS_TERM_B] = r.z_max * 65535.0f / (r.z_max - r.z_min);
-      state[RS_N_VISIBLE] = (float)f.n_visible;
-      for (int k = 0; k < M3T_MAX_RENDERER_BODIES; ++k)
-        state[RS_VISIBLE0 + k] = (f.visible_mask >> k & 1u) ? 1.0f : 0.0f;
-    }
-  }
-  if (f.n_visible == 0) return;  // block-uniform
-  const int S = r.image_size;
-  RasterSurvivor* list = static_cast<RasterSurvivor*>(r.survivors);
-  const int tid = threadIdx.x, nt = blockDim.x, lane = tid & (kWave - 1);
-  for (int order = 0; order < r.n_bodies; ++order) {
-    const M44 trans = mul44(f.P, mul44(load44(cam.world2camera),
-                                       mul44(load44(body_poses + 16 * r.body[order]), load44(r.geometry2body[order]))));
-    const uint32_t low_bits = ((uint32_t)order << 8) | (r.silhouette ? (uint32_t)r.id[order] : 0u);
-    const float* vertices = r.vertices[order];
-    const int* triangles = r.triangles[order];
-    const bool culling = r.culling[order] != 0;
-    const int per_slice = (r.n_triangles[order] + gridDim.x - 1) / gridDim.x;
-    const int t_begin = blockIdx.x * per_slice;
-    const int t_end = min(t_begin + per_slice, r.n_triangles[order]);
-    // A slice is tens of trips long at 128 pairs and a trip is two dependent loads (indices, then the vertices they
-    // name -- the meshes of 64 objects do not stay in L2) in front of ~400 instructions, at two waves per SIMD: the
-    // loads run two trips ahead -- the indices of trip i + 2 and the vertices of trip i + 1 are on their way while
-    // trip i is set up (round 5, 128 pairs x 2 slices: 49.5 -> 45 us with the indices alone -> 41.4 us).  Measured
-    // and not kept, all with identical images: the body's vertices snapped once into an LDS table and the triangles
-    // set up from it (a third of the instructions, 41.9 us: the trips are chains of dependent f64 operations at two
-    // waves per SIMD, not instruction issue), two triangles per thread and trip on top of that (41.8), the list
-    // append's atomic answered one trip later (57: registers), a 128-VGPR build with two workgroups per CU (46.9)
-    int idx1[3] = {0, 0, 0}, idx2[3] = {0, 0, 0};
-    float xyz1[9];
-#pragma unroll
-    for (int k = 0; k < 9; ++k) xyz1[k] = 0.0f;
-    auto load_indices = [&](int t, int (&index)[3]) {
-      if (t < t_end) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) index[k] = triangles[t * 3 + k];
-      }
-    };
-    auto load_vertices = [&](int t, const int (&index)[3], float (&xyz)[9]) {
-      if (t < t_end) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-          const float* p = vertices + (size_t)index[k] * 3;
-          xyz[3 * k] = p[0]; xyz[3 * k + 1] = p[1]; xyz[3 * k + 2] = p[2];
-        }
-      }
-    };
-    load_indices(t_begin + tid, idx1);
-    load_indices(t_begin + nt + tid, idx2);
-    load_vertices(t_begin + tid, idx1, xyz1);
-    for (int base = t_begin; base < t_end; base += nt) {
-      const int t = base + tid;
-      float xyz[9];
-#pragma unroll
-      for (int k = 0; k < 9; ++k) xyz[k] = xyz1[k];
-#pragma unroll
-      for (int k = 0; k < 3; ++k) idx1[k] = idx2[k];
-      load_vertices(t + nt, idx1, xyz1);
-      load_indices(t + 2 * nt, idx2);
-      RasterSurvivor sv;
-      const bool ok = t < t_end && raster_setup_vertices(trans, xyz, culling, S, sv.tri);
-      // one atomic per wave: the lanes with a survivor take consecutive entries
-      const unsigned long long mask = __builtin_amdgcn_ballot_w64(ok);
-      if (mask == 0) continue;  // wave-uniform
-      int first = 0;
-      if (lane == 0) first = atomicAdd(r.n_survivors, __builtin_popcountll(mask));
-      first = __builtin_amdgcn_readfirstlane(first);
-      if (ok) {
-        const int at = first + __builtin_popcountll(mask & ((1ull << lane) - 1ull));
-        if (at < r.survivor_capacity) {
-          sv.low_bits = low_bits;
-          sv.pad = 0;
-          list[at] = sv;
-        }
-      }
-    }
-  }
+#include "m3t_render_setup.inc"
 }
 
 // grid: (bands, renderers).  A workgroup owns a band of image rows: its z-buffer band lives in LDS, it looks at every
@@ -288,117 +203,33 @@ focused_setup_kernel(const RendererDev* renderers, const int* which, const Camer
 // probe scene's ~1 200 survivors, the three-launch form 98 us).  The workgroup that finishes last resets the counters.
 __global__ void __launch_bounds__(M3T_BLOCK_THREADS)
 focused_resolve_kernel(const RendererDev* renderers, const int* which) {
-  extern __shared__ uint32_t lds_z[];  // [band rows * S] packed words, then first_item[threads + 1], wave_total[16]
-  // Every survivor's rows inside the band are cut into pieces of kPiece pixels; the pieces of ALL survivors of a trip
-  // are numbered through (block-wide prefix sum) and dealt out evenly: a covered pixel costs ~30 f64 operations, and a
-  // thread that finished a 100-pixel box by itself kept its whole wave waiting (measured: 54 us per resolve).
-  constexpr int kPiece = 8, kPer = 4;  // survivors a thread looks at per trip: one trip up to 2048 survivors
-  // grid: (renderer pairs, bands) -- workgroup b runs on XCD b mod 8, so with the pair as the fast index the bands of a
-  // pair share an XCD (whenever the number of pairs is a multiple of 8) and its survivor list is fetched into ONE L2:
-  // round 5, 128 pairs x 8 bands -- with the band as the fast index each of the eight L2s read all 12 MB of lists
-  const RendererDev& r = renderers[which[2 * blockIdx.x]];
-  const int twin = which[2 * blockIdx.x + 1];  // a renderer whose rendering is this one (focused_setup_kernel), or -1
-  const int S = r.image_size;
-  const int n_bands = (int)gridDim.y;
-  const int band_rows = (S + n_bands - 1) / n_bands;
-  const int row_lo = (int)blockIdx.y * band_rows, row_hi = min(row_lo + band_rows, S) - 1;  // inclusive
-  const int n_px = band_rows * S;
-  const int tid = threadIdx.x, nt = blockDim.x, lane = tid & (kWave - 1), wave = tid / kWave;
-  int* first_item = reinterpret_cast<int*>(lds_z + n_px);  // [nt + 1]: pieces before thread t's survivors
-  int* wave_total = first_item + nt + 1;                   // [16]
-  int* own_count = wave_total + 16;                        // [kPer][nt]: pieces of thread t's j-th survivor
-  for (int i = tid; i < n_px; i += nt) lds_z[i] = 0xffffffffu;
-  const int n = min(__hip_atomic_load(r.n_survivors, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), r.survivor_capacity);
-  const RasterSurvivor* list = static_cast<const RasterSurvivor*>(r.survivors);
-  auto sink = [S, row_lo](int px, int py, uint32_t word) { atomicMin(&lds_z[(py - row_lo) * S + px], word); };
-  for (int base = 0; base < n && row_lo <= row_hi; base += nt * kPer) {  // block-uniform trip count
-    int mine = 0, cnt[kPer];
-#pragma unroll
-    for (int j = 0; j < kPer; ++j) {
-      const int i = base + j * nt + tid;
-      cnt[j] = 0;
-      if (i < n) {
-        const RasterTriangle& tri = list[i].tri;
-        const int ya = max(tri.y0, row_lo), yb = min(tri.y1, row_hi);
-        if (ya <= yb) cnt[j] = ((tri.x1 - tri.x0 + kPiece) / kPiece) * (yb - ya + 1);
-      }
-      mine += cnt[j];
-    }
-    // inclusive prefix sum over the wave (DPP: row_shr 1 2 4 8, row_bcast 15 / 31), then over the waves
-    int incl = mine;
-    incl += dpp_zero_i<0x111, 0xf>(incl);
-    incl += dpp_zero_i<0x112, 0xf>(incl);
-    incl += dpp_zero_i<0x114, 0xf>(incl);
-    incl += dpp_zero_i<0x118, 0xf>(incl);
-    incl += dpp_zero_i<0x142, 0xa>(incl);
-    incl += dpp_zero_i<0x143, 0xc>(incl);
-    __syncthreads();  // (the previous trip's pieces are done with the tables; the first time: the cleared z-buffer)
-    if (lane == kWave - 1) wave_total[wave] = incl;
-#pragma unroll
-    for (int j = 0; j < kPer; ++j) own_count[j * nt + tid] = cnt[j];
-    __syncthreads();
-    int before = 0;
-    for (int wv = 0; wv < wave; ++wv) before += wave_total[wv];
-    first_item[tid] = before + incl - mine;
-    if (tid == nt - 1) first_item[nt] = before + incl;
-    __syncthreads();
-    const int total = first_item[nt];
-    for (int k = tid; k < total; k += nt) {
-      int lo = 0, hi = nt - 1;  // the last thread whose first piece is <= k (threads without pieces repeat the value:
-      while (lo < hi) {         // the last of equals is the one that owns the piece)
-        const int mid = (lo + hi + 1) >> 1;
-        if (first_item[mid] <= k) lo = mid; else hi = mid - 1;
-      }
-      int local = k - first_item[lo], j = 0;
-      while (j < kPer - 1 && local >= own_count[j * nt + lo]) { local -= own_count[j * nt + lo]; ++j; }
-      const RasterSurvivor& sv = list[base + j * nt + lo];
-      const int ya = max(sv.tri.y0, row_lo);
-      const int pieces = (sv.tri.x1 - sv.tri.x0 + kPiece) / kPiece;
-      const int row = local / pieces, xa = sv.tri.x0 + (local - row * pieces) * kPiece;
-      raster_row(sv.tri, ya + row, xa, min(xa + kPiece - 1, sv.tri.x1), sv.low_bits, sink);
-    }
-  }
-  __syncthreads();
-  const int n_out = (row_hi - row_lo + 1) * S;
-  // four pixels per thread and store where the band allows it (its first pixel and its length multiples of four: the
-  // images come from hipMalloc): one 8-byte and one 4-byte store instead of four 2-byte and four 1-byte ones -- the
-  // output of 128 pairs cost 10.7 of the launch's 69 us (round 5, probe builds)
-  const RendererDev* t = twin >= 0 ? &renderers[twin] : nullptr;  // the same rendering with the twin's id byte: the
-  const size_t first = (size_t)row_lo * S;                        // winner's draw order sits in bits 8..15
-  auto depth_of = [](uint32_t v) { return v == 0xffffffffu ? (uint32_t)65535 : v >> 16; };
-  auto id_of = [](uint32_t v) { return v == 0xffffffffu ? 0u : (v & 0xffu); };
-  auto twin_id_of = [t](uint32_t v) { return (v == 0xffffffffu || !t->silhouette) ? 0u : (uint32_t)(uint8_t)t->id[(v >> 8) & 0xffu]; };
-  if ((first & 3) == 0 && (n_out & 3) == 0) {
-    for (int i = tid * 4; i < n_out; i += nt * 4) {
-      const uint32_t v0 = lds_z[i], v1 = lds_z[i + 1], v2 = lds_z[i + 2], v3 = lds_z[i + 3];
-      const uint2 d = make_uint2(depth_of(v0) | depth_of(v1) << 16, depth_of(v2) | depth_of(v3) << 16);
-      *reinterpret_cast<uint2*>(r.depth_image + first + i) = d;
-      *reinterpret_cast<uint32_t*>(r.silhouette_image + first + i) =
-          id_of(v0) | id_of(v1) << 8 | id_of(v2) << 16 | id_of(v3) << 24;
-      if (t) {
-        *reinterpret_cast<uint2*>(t->depth_image + first + i) = d;
-        *reinterpret_cast<uint32_t*>(t->silhouette_image + first + i) =
-            twin_id_of(v0) | twin_id_of(v1) << 8 | twin_id_of(v2) << 16 | twin_id_of(v3) << 24;
-      }
-    }
-  } else {
-    for (int i = tid; i < n_out; i += nt) {
-      const uint32_t v = lds_z[i];
-      r.depth_image[first + i] = (uint16_t)depth_of(v);
-      r.silhouette_image[first + i] = (uint8_t)id_of(v);
-      if (t) {
-        t->depth_image[first + i] = (uint16_t)depth_of(v);
-        t->silhouette_image[first + i] = (uint8_t)twin_id_of(v);
-      }
-    }
-  }
-  // every band has read the count by now once it says it is done: the last one clears the list for the next rendering
-  if (tid == 0) {
-    if (atomicAdd(r.n_survivors + 1, 1) == n_bands - 1) {
-      __hip_atomic_store(r.n_survivors, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(r.n_survivors + 1, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
+#include "m3t_render_resolve.inc"
+}
+
+// ---- the two-launch form behind a judgement that may reset (m3t_hip_judge_set_reset_renderers) ----
+// Pair p of `which` is rendered iff the judge flagged one of its readers: the entries readers[reader_first[p] ..
+// reader_first[p + 1]) of the judge's list, those whose reset target has a region modality that reads the renderer or
+// its twin.  The test is block-uniform and both kernels form it from the same words -- the judge kernels wrote the
+// flags before the first of them and nobody writes them in between -- so a pair is set up and resolved or neither:
+// the resolve kernel's "last workgroup resets the counters" finds the counters it expects.  A skipped pair stores
+// nothing.  always != 0 (a developer switch of the host): every pair runs.
+__device__ __forceinline__ bool focused_pair_flagged(const int* flags, const int* reader_first, const int* readers, int p) {
+  const int begin = reader_first[p], end = reader_first[p + 1];
+  for (int k = begin; k < end; ++k)
+    if (flags[readers[k]] != 0) return true;
+  return false;
+}
+__global__ void __launch_bounds__(M3T_BLOCK_THREADS)
+focused_setup_flagged_kernel(const RendererDev* renderers, const int* which, const CameraDev* cams, const float* body_poses,
+                             const int* flags, const int* reader_first, const int* readers, int always) {
+  if (!always && !focused_pair_flagged(flags, reader_first, readers, (int)blockIdx.y)) return;  // block-uniform
+#include "m3t_render_setup.inc"
+}
+__global__ void __launch_bounds__(M3T_BLOCK_THREADS)
+focused_resolve_flagged_kernel(const RendererDev* renderers, const int* which, const int* flags, const int* reader_first,
+                               const int* readers, int always) {
+  if (!always && !focused_pair_flagged(flags, reader_first, readers, (int)blockIdx.x)) return;  // block-uniform
+#include "m3t_render_resolve.inc"
 }
 
 // 3/3: unpack into the u16 depth image and the u8 id image (grid: 16 x renderers)

@@ -137,6 +137,85 @@ def evaluate_rbot_sequences(tracker, bodies, poses_gt_per_body, load_images, n_f
     return frames, averages
 
 
+def evaluate_rbot_occlusion_sequences(tracker, bodies, occluders, poses_first_per_run, poses_second_per_run,
+                                      load_images, n_frames, judge_on_device=False,
+                                      judge_occluder_on_own_pose=False):
+    """RBOTEvaluator::EvaluateRunConfiguration (rbot_evaluator.cpp:174-210) with run_configuration.occlusions for N
+    independent runs in ONE context (HIP library): run j tracks bodies[j] and occluders[j], whose region modalities
+    read one FocusedBasicDepthRenderer (ModelOcclusions).  Start: ResetBody(0), then ResetOcclusionBody(0) (:184-185).
+    Cycle i, to the letter of :189-208:
+      1. the tracking step on image i + 1;
+      2. the main body is judged against poses_first[i + 1]; lost: ResetBody -- its pose, the start-modality
+         renderers, StartModality(0, 0) of its modalities;
+      3. the MAIN body's pose, as it then is, is judged against poses_second[i + 1] (:204 passes body_ptr, not the
+         occluding body); lost: ResetOcclusionBody -- the occluder's pose, the renderers, its modalities.
+    judge_occluder_on_own_pose: step 3 judges the occluder's own pose instead (the evident intent; not the reference).
+    The lost bodies of a frame take ONE Tracker.ResetBodies call per step 2 and 3 (every run has a renderer of its own,
+    so each run sees what a tracker of its own would).  Only the main bodies' results are kept.
+    judge_on_device: two judges per context, called one after the other behind the step, both with
+    set_reset_renderers: the first lists the main bodies, the second the main bodies with the occluders as reset targets
+    (judge_occluder_on_own_pose: the occluders themselves); no Sync() and no pose read per frame, the first judge's
+    rows are read once after the last frame.  Returns (per-run lists of per-frame results, per-run averages)."""
+    n = len(bodies)
+    keys = ("translation_error", "rotation_error", "tracking_success", "complete_cycle")
+    load_images(0)
+    if not tracker.ResetBodies(bodies, [poses[0] for poses in poses_first_per_run], 0):
+        raise RuntimeError("ResetBodies failed")
+    if not tracker.ResetBodies(occluders, [poses[0] for poses in poses_second_per_run], 0):
+        raise RuntimeError("ResetBodies failed")
+    frames = [[] for _ in bodies]
+    if judge_on_device:
+        judge_main = tracker.CreateJudge(bodies, max(1, n_frames))
+        judge_main.set_reset_renderers(True)
+        judge_occluder = tracker.CreateJudge(occluders if judge_occluder_on_own_pose else bodies, max(1, n_frames))
+        judge_occluder.set_reset_renderers(True)
+        if not judge_occluder_on_own_pose:
+            for j in range(n):
+                judge_occluder.set_reset_target(j, occluders[j])
+        t0 = time.perf_counter()
+        for i in range(n_frames):
+            load_images(i + 1)
+            if not tracker.ExecuteTrackingStep(i):
+                raise RuntimeError("tracking step %d failed" % i)
+            judge_main.judge([poses[i + 1] for poses in poses_first_per_run], 0)
+            judge_occluder.judge([poses[i + 1] for poses in poses_second_per_run], 0)
+        rows = judge_main.read(0, n_frames)
+        if n_frames:
+            judge_occluder.read(n_frames - 1, 1)  # (the loop's time includes its last launches)
+        dt = (time.perf_counter() - t0) * 1e6 / max(1, n_frames)
+        for i in range(n_frames):
+            for j in range(n):
+                r = rows[i, j]
+                frames[j].append(dict(frame_index=i, translation_error=float(r["translation_error"]),
+                                      rotation_error=float(r["rotation_error"]),
+                                      tracking_success=float(r["tracking_success"]), complete_cycle=dt))
+        averages = [{k: float(np.mean([f[k] for f in fs])) for k in keys} for fs in frames]
+        return frames, averages
+    for i in range(n_frames):
+        load_images(i + 1)
+        t0 = time.perf_counter()
+        ok = tracker.ExecuteTrackingStep(i) and tracker.Sync()
+        dt = (time.perf_counter() - t0) * 1e6
+        if not ok:
+            raise RuntimeError("tracking step %d failed" % i)
+        lost = []
+        for j in range(n):
+            t_err, r_err, success = rbot_pose_result(bodies[j].body2world_pose(), poses_first_per_run[j][i + 1])
+            frames[j].append(dict(frame_index=i, translation_error=t_err, rotation_error=r_err,
+                                  tracking_success=success, complete_cycle=dt))
+            if success == 0.0:
+                lost.append(j)
+        if lost and not tracker.ResetBodies([bodies[j] for j in lost], [poses_first_per_run[j][i + 1] for j in lost], 0):
+            raise RuntimeError("ResetBodies failed")
+        judged = occluders if judge_occluder_on_own_pose else bodies
+        lost = [j for j in range(n)
+                if rbot_pose_result(judged[j].body2world_pose(), poses_second_per_run[j][i + 1])[2] == 0.0]
+        if lost and not tracker.ResetBodies([occluders[j] for j in lost], [poses_second_per_run[j][i + 1] for j in lost], 0):
+            raise RuntimeError("ResetBodies failed")
+    averages = [{k: float(np.mean([f[k] for f in fs])) for k in keys} for fs in frames]
+    return frames, averages
+
+
 # ---------------------------------------------------------------------------------------------------------
 # YCB-Video
 # ---------------------------------------------------------------------------------------------------------
@@ -505,6 +584,8 @@ RBOT_INTRINSICS = (650.048, 647.183, 324.328 - 0.5, 257.323 - 0.5, 640, 512)  # 
 RBOT_BODY_NAMES = ("ape", "bakingsoda", "benchviseblue", "broccolisoup", "cam", "can", "cat", "clown", "cube", "driller",
                    "duck", "eggbox", "glue", "iron", "koalacandy", "lamp", "phone", "squirrel")
 RBOT_SEQUENCE_NAMES = ("a_regular", "b_dynamiclight", "c_noisy", "d_occlusion")
+RBOT_OCCLUSION_BODY = "squirrel_small"  # rbot_evaluator.h kOcclusionBodyName
+RBOT_FOCUSED_IMAGE_SIZE = 200           # evaluate_rbot_dataset.cpp:47
 RBOT_REGION_PARAMETERS = dict(  # evaluate_rbot_dataset.cpp:25-44, rbot_evaluator.cpp:267
     n_lines_max=200, use_adaptive_coverage=0, min_continuous_distance=3.0, function_length=8, distribution_length=12,
     function_amplitude=0.36, function_slope=0.0, learning_rate=1.3, scales=[5, 2, 2, 1],
@@ -518,8 +599,9 @@ def evaluate_rbot_dataset(open_context, dataset_directory, external_directory, b
                           sequence_names=RBOT_SEQUENCE_NAMES, n_frames=1000, region_parameters=None,
                           model_parameters=None, tikhonov_parameter_rotation=1000.0,
                           tikhonov_parameter_translation=30000.0, n_corr_iterations=7, n_update_iterations=2,
-                          report=None, shard=(0, 1), batch=1, judge_on_device=False):
-    """RBOTEvaluator::SetUp + Evaluate for the region modality on the un-modelled sequences: for every (sequence,
+                          report=None, shard=(0, 1), batch=1, judge_on_device=False, sequence_occlusions=None,
+                          judge_occluder_on_own_pose=False):
+    """RBOTEvaluator::SetUp + Evaluate for the region modality: for every (sequence,
     body) a tracker on `dataset/<body>/frames/<sequence>NNNN.png`, started at `dataset/poses_first.txt`, reset on
     loss, scored with the 5 cm / 5 degree criterion.  Bodies are `dataset/<body>/<body>.obj` in millimetres
     (LoadSingleBody :527-535), their region models `external/models/<body>_model.bin` — generated on the device
@@ -533,17 +615,27 @@ def evaluate_rbot_dataset(open_context, dataset_directory, external_directory, b
     loader camera and optimizer -- and go through evaluate_rbot_sequences, which resets the lost bodies alone; the
     results are those of batch = 1.
     judge_on_device (HIP library): the batched loop with the judgement and the reset on the device
-    (evaluate_rbot_sequences; with batch = 1 a batch of one)."""
+    (evaluate_rbot_sequences; with batch = 1 a batch of one).
+    sequence_occlusions: one bool per sequence name (None: all false -- the un-modelled sequences alone).  A sequence
+    with True runs with modelled occlusions (SetUpTracker :213-332 without the texture modality): the evaluated body
+    and RBOT_OCCLUSION_BODY, one RendererGeometry holding both, one FocusedBasicDepthRenderer on the run's camera that
+    references both, two region modalities with ModelOcclusions, two rigid optimizers; the occluder follows
+    `dataset/poses_second.txt`; the result's key is (sequence + "_modeled", body), the reference's title.  These runs
+    go through evaluate_rbot_occlusion_sequences (HIP library, whatever `batch`): `batch` such runs -- 2 x batch
+    bodies, batch renderers -- share a context.  judge_occluder_on_own_pose: see there."""
     import os
 
     from . import config as cfg
     from . import generator, host
-    if batch > 1 or judge_on_device:
+    occlusions = list(sequence_occlusions) if sequence_occlusions is not None else [False] * len(sequence_names)
+    if len(occlusions) != len(sequence_names):
+        raise ValueError("sequence_occlusions needs one entry per sequence name")
+    if batch > 1 or judge_on_device or any(occlusions):
         return _evaluate_rbot_dataset_batched(open_context, dataset_directory, external_directory, body_names,
                                               sequence_names, n_frames, region_parameters, model_parameters,
                                               tikhonov_parameter_rotation, tikhonov_parameter_translation,
                                               n_corr_iterations, n_update_iterations, report, shard, max(1, batch),
-                                              judge_on_device)
+                                              judge_on_device, occlusions, judge_occluder_on_own_pose)
     poses_first = read_poses_rbot(os.path.join(dataset_directory, "poses_first.txt"), n_frames)
     region_parameters = dict(RBOT_REGION_PARAMETERS, **(region_parameters or {}))
     model_parameters = dict(RBOT_MODEL_PARAMETERS, **(model_parameters or {}))
@@ -585,37 +677,73 @@ def evaluate_rbot_dataset(open_context, dataset_directory, external_directory, b
 def _evaluate_rbot_dataset_batched(open_context, dataset_directory, external_directory, body_names, sequence_names,
                                    n_frames, region_parameters, model_parameters, tikhonov_parameter_rotation,
                                    tikhonov_parameter_translation, n_corr_iterations, n_update_iterations, report,
-                                   shard, batch, judge_on_device=False):
-    """evaluate_rbot_dataset with up to `batch` runs per context (same runs, same order, same results)"""
+                                   shard, batch, judge_on_device=False, occlusions=None,
+                                   judge_occluder_on_own_pose=False):
+    """evaluate_rbot_dataset with up to `batch` runs per context (same runs, same order, same results).  A context
+    holds runs of one kind: un-modelled ones, or runs with modelled occlusions."""
     import os
 
     from . import config as cfg
     from . import generator, host
     poses_first = read_poses_rbot(os.path.join(dataset_directory, "poses_first.txt"), n_frames)
+    occlusions = list(occlusions) if occlusions is not None else [False] * len(sequence_names)
+    poses_second = (read_poses_rbot(os.path.join(dataset_directory, "poses_second.txt"), n_frames)
+                    if any(occlusions) else None)
     region_parameters = dict(RBOT_REGION_PARAMETERS, **(region_parameters or {}))
     model_parameters = dict(RBOT_MODEL_PARAMETERS, **(model_parameters or {}))
     results = {}
-    runs = [(sequence, name) for sequence in sequence_names for name in body_names][shard[0]::shard[1]]
-    for first in range(0, len(runs), batch):
-        chunk = runs[first:first + batch]
+    runs = [(sequence, name, occluded) for sequence, occluded in zip(sequence_names, occlusions)
+            for name in body_names][shard[0]::shard[1]]
+    chunks = []  # consecutive runs of one kind, up to `batch` of them
+    for run in runs:
+        if chunks and len(chunks[-1]) < batch and chunks[-1][0][2] == run[2]:
+            chunks[-1].append(run)
+        else:
+            chunks.append([run])
+
+    def body_and_model(api, name, model=None):
+        body = generator.Body(api, name, os.path.join(dataset_directory, name, name + ".obj"), 0.001, True, False,
+                              np.eye(4, dtype=F))
+        if model is not None:  # (the context has this body's model already)
+            return body, model
+        model_path = os.path.join(external_directory, "models", name + "_model.bin")
+        if cfg.model_bin_matches(model_path, True, model_parameters, body.body_data()):
+            model = host.RegionModel(api, path=model_path)
+        else:
+            generation = {k: v for k, v in model_parameters.items() if k != "use_random_seed"}
+            model = host.RegionModel.generate(api, body, **generation)
+            cfg.write_model_bin(model_path, True, model_parameters, body.body_data(), *model.views())
+        return body, model
+
+    for chunk in chunks:
         api = open_context()
-        bodies, cameras = [], []
-        for sequence, name in chunk:
-            body = generator.Body(api, name, os.path.join(dataset_directory, name, name + ".obj"), 0.001, True, False,
-                                  np.eye(4, dtype=F))
-            model_path = os.path.join(external_directory, "models", name + "_model.bin")
-            if cfg.model_bin_matches(model_path, True, model_parameters, body.body_data()):
-                model = host.RegionModel(api, path=model_path)
-            else:
-                generation = {k: v for k, v in model_parameters.items() if k != "use_random_seed"}
-                model = host.RegionModel.generate(api, body, **generation)
-                cfg.write_model_bin(model_path, True, model_parameters, body.body_data(), *model.views())
+        occluded = chunk[0][2]
+        bodies, cameras, occluders = [], [], []
+        occluder_model = None  # one per context: every run has its own occluding body, all of them share the model
+        for sequence, name, _ in chunk:
+            body, model = body_and_model(api, name)
             camera = generator.LoaderColorCamera(api, os.path.join(dataset_directory, name, "frames"), RBOT_INTRINSICS,
                                                  sequence, 0, 4)
             modality = host.RegionModality(api, body, camera, model, **region_parameters)
+            if occluded:  # SetUpTracker :236-256, :268-269, :293-327
+                occluder, occluder_model = body_and_model(api, RBOT_OCCLUSION_BODY, occluder_model)
+                geometry = host.RendererGeometry(api)
+                geometry.AddBody(body)
+                geometry.AddBody(occluder)
+                renderer = host.FocusedBasicDepthRenderer(api, geometry, camera, image_size=RBOT_FOCUSED_IMAGE_SIZE)
+                renderer.AddReferencedBody(body)
+                renderer.AddReferencedBody(occluder)
+                modality.ModelOcclusions(renderer)
             host.Optimizer(api, body=body, modalities=[modality],
                            tikhonov_parameter_rotation=tikhonov_parameter_rotation,
                            tikhonov_parameter_translation=tikhonov_parameter_translation)
+            if occluded:
+                occluder_modality = host.RegionModality(api, occluder, camera, occluder_model, **region_parameters)
+                occluder_modality.ModelOcclusions(renderer)
+                host.Optimizer(api, body=occluder, modalities=[occluder_modality],
+                               tikhonov_parameter_rotation=tikhonov_parameter_rotation,
+                               tikhonov_parameter_translation=tikhonov_parameter_translation)
+                occluders.append(occluder)
             bodies.append(body)
             cameras.append(camera)
         tracker = host.Tracker(api, n_corr_iterations, n_update_iterations)
@@ -626,12 +754,18 @@ def _evaluate_rbot_dataset_batched(open_context, dataset_directory, external_dir
                 if not camera.UpdateImage():
                     raise RuntimeError("Could not read image from %s" % camera.image_path())
 
-        _, averages = evaluate_rbot_sequences(tracker, bodies, [poses_first] * len(chunk), load_images, n_frames,
-                                              judge_on_device=judge_on_device)
-        for (sequence, name), average in zip(chunk, averages):
-            results[(sequence, name)] = average
+        if occluded:
+            _, averages = evaluate_rbot_occlusion_sequences(
+                tracker, bodies, occluders, [poses_first] * len(chunk), [poses_second] * len(chunk), load_images,
+                n_frames, judge_on_device=judge_on_device, judge_occluder_on_own_pose=judge_occluder_on_own_pose)
+        else:
+            _, averages = evaluate_rbot_sequences(tracker, bodies, [poses_first] * len(chunk), load_images, n_frames,
+                                                  judge_on_device=judge_on_device)
+        for (sequence, name, _), average in zip(chunk, averages):
+            key = sequence + "_modeled" if occluded else sequence
+            results[(key, name)] = average
             if report is not None:
-                report(sequence + "_" + name, average)
+                report(key + "_" + name, average)
     keys = ("translation_error", "rotation_error", "tracking_success", "complete_cycle")
     overall = {k: float(np.mean([r[k] for r in results.values()])) for k in keys}
     return results, overall

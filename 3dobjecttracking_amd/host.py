@@ -170,6 +170,18 @@ class Judge:
         g = None if geometry2body is None else fptr(pose_arg(geometry2body))
         self.api.call("judge_set_add_only", self.id, int(index), g)
 
+    def set_reset_renderers(self, enable=True):
+        """a resetting `judge` may run the start-modality renderers (ModelOcclusions / UseRegionChecking) that the
+        region modalities of the bodies it resets read -- each once, decided on the device, nothing when no body is
+        lost; off (the default): such bodies are refused"""
+        self.api.call("judge_set_reset_renderers", self.id, int(bool(enable)))
+
+    def set_reset_target(self, body, target=None):
+        """entry `body` (a listed Body or its index in the list) is judged on its own pose as before, but when it is
+        found lost `target` (a Body; None: the listed body again) takes the entry's ground-truth pose and the restart"""
+        index = body if isinstance(body, (int, np.integer)) else [b.id for b in self.bodies].index(body.id)
+        self.api.call("judge_set_reset_target", self.id, int(index), -1 if target is None else int(target.id))
+
     def raw_judge(self, gt_poses, reset_iteration=-1):
         """(status, row) without raising"""
         assert len(gt_poses) == len(self.bodies)

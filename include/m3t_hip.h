@@ -407,7 +407,29 @@ int m3t_hip_reset_structures(m3t_hip_context*, const int* optimizer_ids, int n, 
  * marked keep their judgement and its bits, and a judge may mix both kinds.  Curve and area under curve stay with the
  * host (three f32 operations from add_error).  The call waits for the stream and uploads (outside the frame loop);
  * M3T_ERR_INVALID_ARGUMENT: a bad judge or index, rows already judged (judge_clear first), a non-finite entry of the
- * pose. */
+ * pose.
+ * Start-modality renderers (judge_set_reset_renderers; off by default, and then the refusal above stands).  With it on,
+ * a resetting judge_bodies call has the contract of ONE reset_bodies call on the list of bodies the device finds lost:
+ * the poses of all lost bodies are written; then every start-modality renderer that a region modality of at least one
+ * lost body reads (model_occlusions: its depth renderer, use_region_checking: its silhouette renderer) is rendered
+ * once, with the poses after all of the call's resets -- a renderer and its twin (same camera, geometry, referenced
+ * bodies, depth range and image size) together; then StartModality of the lost bodies' region modalities runs.  Every
+ * other body, every renderer no lost body reads (unless its twin is read) and every renderer of a call in which nobody
+ * is lost keep their images, crop, visibility and survivor counters bit for bit.  The host does not know whether a
+ * renderer ran, so its "has rendered" mirror (renderer_get_images) is left as it was.  Only the two-launch form of the
+ * renderers (z-buffer band in LDS) is covered: M3T_ERR_UNSUPPORTED, naming the image size, when a renderer's band does
+ * not fit the LDS or the LDS form is off (M3T_HIP_NO_LDS_RASTER).  The other refusals of a resetting call stay.
+ * Developer switch: with M3T_HIP_JUDGE_RENDER_ALWAYS in the environment (read once per context, at its first
+ * judge_bodies call) every pair such a call lists is rendered whether a reader is lost or not; results are those of
+ * extra start_rendering calls.  tools/occlusion_judge_timing.py measures the skip against it.
+ * Reset targets (judge_set_reset_target).  Entry `index` keeps being judged on its listed body's pose; when it is found
+ * lost, body_id -- not the listed body -- takes the entry's ground-truth pose and the restart (RBOTEvaluator judges the
+ * occluding body through the main body's pose, examples/rbot_evaluator.cpp:201-208).  was_reset and the refusals of a
+ * resetting call refer to the target, and the call's region modalities and renderers are the targets'; a judge-only
+ * call ignores targets.  body_id = -1 restores the default.  The call waits for the stream and uploads (outside the
+ * frame loop).  M3T_ERR_INVALID_ARGUMENT, nothing changed: a bad judge, index or body id; rows already judged
+ * (judge_clear first); a body that two entries of the judge would write, as target or as own listed body; a body that
+ * another entry lists (that entry reads the pose the reset would write). */
 int m3t_hip_judge_create(m3t_hip_context*, const int* body_ids, int n_bodies, int n_rows_max, int* judge);
 int m3t_hip_judge_set_thresholds(m3t_hip_context*, int judge, float translation_error_threshold,
                                  float rotation_error_threshold);
@@ -423,6 +445,8 @@ int m3t_hip_judge_read_structures(m3t_hip_context*, int judge, int first_row, in
                                   m3t_structure_judgement* out /* [n_rows][n_structures] */);
 int m3t_hip_judge_set_add_only(m3t_hip_context*, int judge, int index,
                                const float* geometry2body_pose /* 16, column-major, or NULL: identity */);
+int m3t_hip_judge_set_reset_renderers(m3t_hip_context*, int judge, int enable);
+int m3t_hip_judge_set_reset_target(m3t_hip_context*, int judge, int index, int body_id /* -1: the listed body */);
 /* OPTEvaluator::CalculateDiameters (examples/opt_evaluator.cpp:580-600): the largest distance between two of n_vertices
  * vertices (xyz, 3 floats each), by exhaustive search on the device.  For every pair, in f32, every operation rounded,
  * no contraction: dx = xi - xj, dy, dz likewise, d2 = (dx*dx + dy*dy) + dz*dz -- the order of the judge's other norms --

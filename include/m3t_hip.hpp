@@ -492,6 +492,15 @@ class Tracker {
     void SetAddOnly(int index, const Pose* geometry2body = nullptr) {
       c_->Check(m3t_hip_judge_set_add_only(c_->get(), id_, index, geometry2body ? geometry2body->data() : nullptr), "Judge");
     }
+    // a resetting JudgeBodies may run the start-modality renderers of the bodies it resets, decided on the device
+    void SetResetRenderers(bool enable = true) {
+      c_->Check(m3t_hip_judge_set_reset_renderers(c_->get(), id_, enable ? 1 : 0), "Judge");
+    }
+    // listed body `index` is judged on its own pose; found lost, `target` takes its ground truth and the restart
+    // (nullptr: the listed body again)
+    void SetResetTarget(int index, const Body* target) {
+      c_->Check(m3t_hip_judge_set_reset_target(c_->get(), id_, index, target ? target->id() : -1), "Judge");
+    }
     int JudgeBodies(const std::vector<Pose>& gt_body2world_poses, int reset_iteration = -1) {
       int row = -1;
       if (gt_body2world_poses.size() != n_) return -1;

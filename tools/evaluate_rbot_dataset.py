@@ -1,12 +1,16 @@
-"""examples/evaluate_rbot_dataset.cpp over the device context (region modality, sequences without modelled
-occlusions):
+"""examples/evaluate_rbot_dataset.cpp over the device context (region modality; the sequences without modelled
+occlusions, with --modeled-occlusions also the reference's fifth column):
 
-    python tools/evaluate_rbot_dataset.py [--batch N] [--judge-on-device] RBOT_DATASET_DIR EXTERNAL_DIR [body ...]
+    python tools/evaluate_rbot_dataset.py [--batch N] [--judge-on-device] [--modeled-occlusions]
+                                          RBOT_DATASET_DIR EXTERNAL_DIR [body ...]
 
 --batch N: up to N runs share one device context (each with its own body, model, camera and optimizer); a lost body is
 reset alone (m3t_hip_reset_bodies), so the results are those of one context per run.
 --judge-on-device: the 5 cm / 5 degree judgement and the reset are the device's (m3t_hip_judge_bodies): no wait and no
 pose read per frame; "complete cycle" is then the loop's wall time per frame.
+--modeled-occlusions: d_occlusion once more behind the four sequences, with squirrel_small tracked along
+poses_second.txt and modelled occlusions on both region modalities (evaluation.evaluate_rbot_dataset,
+sequence_occlusions); without the flag the output is that of the four sequences alone.
 Prints the success rate and the mean step time per (sequence, body) and overall, like
 RBOTEvaluator::VisualizeFinalResult."""
 import importlib
@@ -33,6 +37,9 @@ if __name__ == "__main__":
     judge_on_device = "--judge-on-device" in argv
     if judge_on_device:
         argv.remove("--judge-on-device")
+    modeled = "--modeled-occlusions" in argv
+    if modeled:
+        argv.remove("--modeled-occlusions")
     if "--batch" in argv:
         at = argv.index("--batch")
         if at + 1 >= len(argv) or not argv[at + 1].isdigit() or int(argv[at + 1]) < 1:
@@ -40,9 +47,13 @@ if __name__ == "__main__":
         batch = int(argv[at + 1])
         del argv[at:at + 2]
     if len(argv) < 2:
-        sys.exit("usage: evaluate_rbot_dataset.py [--batch N] [--judge-on-device] RBOT_DATASET_DIR EXTERNAL_DIR [body ...]")
+        sys.exit("usage: evaluate_rbot_dataset.py [--batch N] [--judge-on-device] [--modeled-occlusions] "
+                 "RBOT_DATASET_DIR EXTERNAL_DIR [body ...]")
     ev = pkg.evaluation
     bodies = argv[2:] or ev.RBOT_BODY_NAMES
+    kw = {}
+    if modeled:  # evaluate_rbot_dataset.cpp:17-20
+        kw = dict(sequence_names=ev.RBOT_SEQUENCE_NAMES + ("d_occlusion",), sequence_occlusions=[False] * 4 + [True])
     _, overall = ev.evaluate_rbot_dataset(lambda: pkg.open_context(local_rank), argv[0], argv[1], bodies, report=report,
-                                          shard=(rank, world), batch=batch, judge_on_device=judge_on_device)
+                                          shard=(rank, world), batch=batch, judge_on_device=judge_on_device, **kw)
     report("all_sequences_all_bodies", overall)
