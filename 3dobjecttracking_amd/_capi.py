@@ -175,6 +175,55 @@ class DepthModalityParams(C.Structure):
             self.standard_deviations[i] = float(v[i]) if i < len(v) else 0.0
 
 
+class TextureModalityParams(C.Structure):
+    """m3t_texture_modality_params; defaults = M3T/include/m3t/texture_modality.h:400-407, 431-436."""
+    _fields_ = [
+        ("descriptor_bytes", C.c_int), ("focused_image_size", C.c_int),
+        ("descriptor_distance_threshold", C.c_float), ("tukey_norm_constant", C.c_float),
+        ("n_standard_deviations", C.c_int), ("standard_deviations", C.c_float * M3T_MAX_SCALES),
+        ("max_keyframe_rotation_difference", C.c_float), ("max_keyframe_age", C.c_int), ("n_keyframes", C.c_int),
+        ("measure_occlusions", C.c_int), ("measured_occlusion_radius", C.c_float),
+        ("measured_occlusion_threshold", C.c_float), ("modeled_occlusion_radius", C.c_float),
+        ("modeled_occlusion_threshold", C.c_float),
+    ]
+
+    def __init__(self, **kw):
+        super().__init__()
+        self.descriptor_bytes = 32
+        self.focused_image_size = 200
+        self.descriptor_distance_threshold = 0.7
+        self.tukey_norm_constant = 20.0
+        self.set_standard_deviations([15.0, 5.0])
+        self.max_keyframe_rotation_difference = float(np.float32(10.0) * np.float32(np.pi) / np.float32(180.0))
+        self.max_keyframe_age = 100
+        self.n_keyframes = 1
+        self.measured_occlusion_radius = 0.01
+        self.measured_occlusion_threshold = 0.03
+        self.modeled_occlusion_radius = 0.01
+        self.modeled_occlusion_threshold = 0.03
+        for k, v in kw.items():
+            if k == "standard_deviations":
+                self.set_standard_deviations(v)
+            else:
+                if not hasattr(self, k):
+                    raise AttributeError(k)
+                setattr(self, k, v)
+
+    def set_standard_deviations(self, v):
+        self.n_standard_deviations = len(v)
+        for i in range(M3T_MAX_SCALES):
+            self.standard_deviations[i] = float(v[i]) if i < len(v) else 0.0
+
+
+class TextureDataPoint(C.Structure):
+    _fields_ = [("center_f_body", C.c_float * 3), ("center_f_camera", C.c_float * 3), ("center", C.c_float * 2),
+                ("correspondence_center", C.c_float * 2)]
+
+
+M3T_MAX_TEXTURE_FEATURES = 4096
+M3T_MAX_TEXTURE_KEYFRAMES = 8
+
+
 class DataLine(C.Structure):
     _fields_ = [("center_f_body", C.c_float * 3), ("center_u", C.c_float), ("center_v", C.c_float),
                 ("normal_u", C.c_float), ("normal_v", C.c_float), ("delta_r", C.c_float),
@@ -227,6 +276,10 @@ DATA_POINT_DTYPE = np.dtype([
     ("center_u", np.float32), ("center_v", np.float32), ("depth", np.float32),
     ("correspondence_center_f_camera", np.float32, 3),
     ("valid", np.int32), ("model_point_index", np.int32)])
+TEXTURE_DATA_POINT_DTYPE = np.dtype([
+    ("center_f_body", np.float32, 3), ("center_f_camera", np.float32, 3), ("center", np.float32, 2),
+    ("correspondence_center", np.float32, 2)])
+assert TEXTURE_DATA_POINT_DTYPE.itemsize == C.sizeof(TextureDataPoint) == 40
 assert DATA_LINE_DTYPE.itemsize == C.sizeof(DataLine)
 assert DATA_POINT_DTYPE.itemsize == C.sizeof(DataPoint)
 
@@ -362,6 +415,12 @@ _HIP_ONLY = {
     "judge_set_reset_renderers": [C.c_int, C.c_int],
     "judge_set_reset_target": [C.c_int, C.c_int, C.c_int],
     "vertices_diameter": [c_float_p, C.c_int, c_float_p],
+    "texture_modality_create": [C.POINTER(TextureModalityParams), C.c_int, C.c_int, C.c_int, C.c_int],
+    "texture_modality_model_occlusions": [C.c_int, C.c_int],
+    "texture_modality_get_region_of_interest": [C.c_int, c_int_p, c_float_p, c_int_p],
+    "texture_modality_set_features": [C.c_int, c_float_p, C.POINTER(C.c_uint8), C.c_int],
+    "texture_modality_get_points": [C.c_int, C.c_void_p, C.c_int, c_int_p],
+    "texture_modality_get_keyframes": [C.c_int, c_int_p, c_int_p, c_int_p, c_float_p, C.c_int],
 }
 
 

@@ -14,6 +14,7 @@
 #include <stdint.h>
 
 #include "../../include/m3t_types.h"
+#include "m3t_texture.h"
 
 // ---- per-line state, field-major: state[field * n_lines_max + line] ----------
 enum {
@@ -167,6 +168,43 @@ struct DepthModDev {
   // 1: the region modality on the same rigid optimizer uses a model with the same view orientations and a camera
   // with the same world2camera pose, so both GetClosestView searches give the same index (set by UploadTables)
   int view_search_shared;
+};
+
+// TextureModality (texture_modality.h:400-436) on the device.  The caller's features, the keyframe ring, the data points
+// and the few words that follow the tracking (which keyframes are held, their age, the orientation of the last one) are
+// written by the modality's kernels only (m3t_texture.hip); the host mirrors nothing of them.
+struct TextureStateDev {
+  int head;           // ring slot of the oldest keyframe held
+  int n_keyframes;    // points_keyframes_.size()
+  int keyframe_age;
+  int n_data_points;  // data_points_.size()
+  float orientation_last_keyframe[4];
+  int counts[M3T_TEXTURE_MAX_KEYFRAMES];  // points per ring slot
+};
+enum { TF_HEADER_WORDS = 4 };  // a feature block: {n, 0, 0, 0} | keypoints [4096][2] | descriptors [4096][words]
+enum { TP_BODY = 0, TP_CAMERA = 3, TP_CENTER = 6, TP_CORRESPONDENCE = 8, TP_FLOATS = 10 };  // m3t_texture_data_point
+struct TextureModDev {
+  int body, camera, depth_camera;
+  int descriptor_words;  // 8 (ORB) or 16 (BRISK, FREAK)
+  int n_keyframes_max;
+  float descriptor_distance_threshold, tukey_norm_constant;
+  int n_standard_deviations;
+  float standard_deviations[M3T_MAX_SCALES];
+  float max_keyframe_rotation_difference;
+  int max_keyframe_age;
+  int measure_occlusions;
+  float measured_occlusion_radius, measured_occlusion_threshold;
+  int model_occlusions, body_id;
+  float modeled_occlusion_radius, modeled_occlusion_threshold;
+  const RendererDev* silhouette_renderer;
+  const RendererDev* depth_renderer;
+  int silhouette_renderer_slot, depth_renderer_slot;
+  const uint32_t* features;         // the feature block the last set_features call copied
+  float* keyframe_points;           // [n_keyframes_max][4096][3]
+  uint32_t* keyframe_descriptors;   // [n_keyframes_max][4096][descriptor_words]
+  float* data_points;               // [n_keyframes_max * 4096][TP_FLOATS]
+  TextureStateDev* state;
+  float* gradient_hessian;          // [6 + 36]
 };
 
 // One rigid body with an unconstrained 6-dof root link (body2joint = I):

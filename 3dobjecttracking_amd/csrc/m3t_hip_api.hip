@@ -28,6 +28,7 @@
 #include "m3t_kernels.hip"
 #include "m3t_judge.hip"
 #include "m3t_opt.hip"
+#include "m3t_texture.hip"
 #include "m3t_compact.hip"
 #include "m3t_render.hip"
 #include "m3t_modelgen.hip"
@@ -185,8 +186,16 @@ struct DepthMod {
   DevMem point_state, gh;
   DepthModDev dev{};
 };
+struct TextureMod {  // TextureModality behind its feature detector (m3t_texture.hip)
+  m3t_texture_modality_params p{};
+  int body, camera, depth_camera, silhouette_renderer, depth_renderer = -1;
+  DevMem features, keyframe_points, keyframe_descriptors, data_points, state, gh;
+  MappedRing uploads;  // set_features: the caller's features cross through page-locked blocks taken in turn
+  TextureModDev dev{};
+};
+enum ModalityKind { kRegionModality, kDepthModality, kTextureModality };
 struct ModalityRef {
-  bool region;
+  ModalityKind kind;
   int index;
 };
 struct Link {
@@ -266,6 +275,7 @@ struct m3t_hip_context {
   std::vector<float> body_poses;  // host mirror [n][16] (valid when !poses_on_device_newer)
   std::vector<std::unique_ptr<RegionMod>> region_mods;
   std::vector<std::unique_ptr<DepthMod>> depth_mods;
+  std::vector<std::unique_ptr<TextureMod>> texture_mods;
   std::vector<ModalityRef> modalities;
   std::vector<std::unique_ptr<SharedHistogramsH>> shared_histograms;
   DevMem d_shared_histograms;
@@ -311,7 +321,7 @@ struct m3t_hip_context {
   int n_corr_iterations = 5, n_update_iterations = 2;
   int fused_mode = 1;
   // device tables
-  DevMem d_cams, d_region, d_depth, d_opts, d_poses, d_scratch_view;
+  DevMem d_cams, d_region, d_depth, d_texture, d_opts, d_poses, d_scratch_view;
   DevMem d_gh_sources, d_gh_all;  // m3t_hip_modalities_get_gradient_hessian
   int gh_sources_count = -1;
   bool tables_dirty = true, cams_dirty = true, slots_dirty = false, poses_dirty_host = true;
@@ -849,6 +859,22 @@ void ComputeLayout(Ctx* ctx) {
   }
 }
 
+// the 42-float g/H block of a modality, whatever its kind (Link::CalculateGradientAndHessian sums them, link.cpp:184-193)
+float* ModalityGhPointer(Ctx* ctx, const ModalityRef& ref) {
+  switch (ref.kind) {
+    case kRegionModality: return ctx->region_mods[ref.index]->gh.as<float>();
+    case kDepthModality: return ctx->depth_mods[ref.index]->gh.as<float>();
+    default: return ctx->texture_mods[ref.index]->gh.as<float>();
+  }
+}
+int ModalityBody(Ctx* ctx, const ModalityRef& ref) {
+  switch (ref.kind) {
+    case kRegionModality: return ctx->region_mods[ref.index]->body;
+    case kDepthModality: return ctx->depth_mods[ref.index]->body;
+    default: return ctx->texture_mods[ref.index]->body;
+  }
+}
+
 void DfsOrder(Ctx* ctx, int link, std::vector<int>* order) {
   order->push_back(link);
   for (int c : ctx->links[link].children) DfsOrder(ctx, c, order);
@@ -913,8 +939,7 @@ int UploadTreeTables(Ctx* ctx) {
       REQUIRE(int(l.modalities.size()) <= M3T_MAX_LINK_MODALITIES, M3T_ERR_UNSUPPORTED, "too many modalities per link");
       d.n_gh = int(l.modalities.size());
       for (int k = 0; k < d.n_gh; ++k) {
-        const ModalityRef& ref = ctx->modalities[l.modalities[k]];
-        d.gh[k] = ref.region ? ctx->region_mods[ref.index]->gh.as<float>() : ctx->depth_mods[ref.index]->gh.as<float>();
+        d.gh[k] = ModalityGhPointer(ctx, ctx->modalities[l.modalities[k]]);
       }
       links.push_back(d);
     }
@@ -1035,11 +1060,16 @@ int UploadTreeTables(Ctx* ctx) {
         st.region_first = 1;
         for (size_t m = 0; m < l.modalities.size(); ++m) {
           const ModalityRef& ref = ctx->modalities[l.modalities[m]];
-          int& slot = ref.region ? st.region_modality : st.depth_modality;
+          ++attached;
+          if (ref.kind == kTextureModality) {  // (the one-launch steps do not know texture modalities)
+            possible = false;
+            continue;
+          }
+          const bool region = ref.kind == kRegionModality;
+          int& slot = region ? st.region_modality : st.depth_modality;
           if (slot >= 0 || l.body < 0) possible = false;  // two of a kind on one link, or a modality without a body
           slot = ref.index;
-          if (m == 0) st.region_first = ref.region ? 1 : 0;
-          ++attached;
+          if (m == 0) st.region_first = region ? 1 : 0;
         }
         steps.push_back(st);
         tracked.push_back(int(k));
@@ -1196,6 +1226,15 @@ int UploadRendererTables(Ctx* ctx) {
     d.silhouette_renderer_slot = d.use_silhouette_checking ? slot_of(m->silhouette_renderer, m->body) : -1;
     if (d.model_occlusions) for_all[m->depth_renderer] = 1;
     if (d.use_silhouette_checking) for_all[m->silhouette_renderer] = 1;
+  }
+  for (auto& m : ctx->texture_mods) {  // start_modality_renderer_ptrs / results_renderer_ptrs :516-524
+    TextureModDev& d = m->dev;
+    d.silhouette_renderer = ctx->d_renderers.as<RendererDev>() + m->silhouette_renderer;
+    d.silhouette_renderer_slot = slot_of(m->silhouette_renderer, m->body);
+    d.depth_renderer = d.model_occlusions ? ctx->d_renderers.as<RendererDev>() + m->depth_renderer : nullptr;
+    d.depth_renderer_slot = d.model_occlusions ? slot_of(m->depth_renderer, m->body) : -1;
+    for_region[m->silhouette_renderer] = 1;
+    if (d.model_occlusions) for_region[m->depth_renderer] = 1;
   }
   std::vector<int> list_region, list_all;
   for (size_t i = 0; i < n; ++i) {
@@ -1537,8 +1576,14 @@ int UploadTables(Ctx* ctx) {
     HIPCHK(ctx->d_depth.alloc(std::max<size_t>(1, d.size()) * sizeof(DepthModDev)));
     if (!r.empty()) HIPCHK(hipMemcpy(ctx->d_region.p, r.data(), r.size() * sizeof(RegionModDev), hipMemcpyHostToDevice));
     if (!d.empty()) HIPCHK(hipMemcpy(ctx->d_depth.p, d.data(), d.size() * sizeof(DepthModDev), hipMemcpyHostToDevice));
+    if (!ctx->texture_mods.empty()) {
+      std::vector<TextureModDev> t(ctx->texture_mods.size());
+      for (size_t i = 0; i < t.size(); ++i) t[i] = ctx->texture_mods[i]->dev;
+      HIPCHK(ctx->d_texture.alloc(t.size() * sizeof(TextureModDev)));
+      HIPCHK(hipMemcpy(ctx->d_texture.p, t.data(), t.size() * sizeof(TextureModDev), hipMemcpyHostToDevice));
+    }
     // kinematic structures (m3t_links.hip) as soon as one optimizer is more than a free rigid body
-    ctx->tree_mode = false;
+    ctx->tree_mode = !ctx->texture_mods.empty();  // a texture modality: the general path, one launch per sub-step
     for (auto& o : ctx->optimizers) {
       if (!ctx->links[o.link].simple || !ctx->links[o.link].children.empty() || !o.constraints.empty() ||
           !o.soft_constraints.empty())
@@ -1547,7 +1592,11 @@ int UploadTables(Ctx* ctx) {
       // and one depth modality per body, the link kernels sum any number (Link::CalculateGradientAndHessian,
       // link.cpp:184-193, in the order they were added)
       int n_region = 0, n_depth = 0;
-      for (int mid : ctx->links[o.link].modalities) (ctx->modalities[mid].region ? n_region : n_depth) += 1;
+      for (int mid : ctx->links[o.link].modalities) {
+        const ModalityKind kind = ctx->modalities[mid].kind;
+        if (kind == kTextureModality) ctx->tree_mode = true;  // the link kernels sum its g/H like any other
+        else (kind == kRegionModality ? n_region : n_depth) += 1;
+      }
       if (n_region > 1 || n_depth > 1) ctx->tree_mode = true;
     }
     if (ctx->tree_mode) {
@@ -1570,7 +1619,7 @@ int UploadTables(Ctx* ctx) {
       od.tikhonov_translation = o.tt;
       for (int mid : l.modalities) {
         const ModalityRef& ref = ctx->modalities[mid];
-        if (ref.region) od.region_modality = ref.index;
+        if (ref.kind == kRegionModality) od.region_modality = ref.index;
         else od.depth_modality = ref.index;
       }
       if (od.region_modality >= 0 && od.depth_modality >= 0) {
@@ -1706,6 +1755,11 @@ int CheckImages(Ctx* ctx) {
     const Camera& d = *ctx->cameras[m->camera];
     REQUIRE(d.has_image[d.current], M3T_ERR_NOT_SET_UP, "Set up depth camera first (no image uploaded)");
   }
+  for (auto& m : ctx->texture_mods) {  // (the colour frame is the caller's detector's; the kernels never read it)
+    if (!m->p.measure_occlusions) continue;
+    const Camera& d = *ctx->cameras[m->depth_camera];
+    REQUIRE(d.has_image[d.current], M3T_ERR_NOT_SET_UP, "Set up depth camera first (no image uploaded)");
+  }
   return M3T_OK;
 }
 
@@ -1744,8 +1798,24 @@ int LaunchHistogram(Ctx* ctx, int iteration, bool initialize, bool behind_guarde
   return M3T_OK;
 }
 
+// TextureModality::StartModality (decide = false) / CalculateResults (decide = true), behind their renderers
+int LaunchTextureKeyframes(Ctx* ctx, bool decide) {
+  const int nt = int(ctx->texture_mods.size());
+  if (nt == 0) return M3T_OK;
+  hipLaunchKernelGGL(texture_keyframe_kernel, dim3(nt), dim3(M3T_TEXTURE_MATCH_THREADS), 0, ctx->stream,
+                     ctx->d_texture.as<TextureModDev>(), ctx->cams_active, ctx->d_poses.as<float>(), decide ? 1 : 0);
+  HIPCHK(hipGetLastError());
+  return M3T_OK;
+}
+
 int LaunchCorrespondences(Ctx* ctx, int iteration, int corr_iteration) {
   int nr = int(ctx->region_mods.size()), nd = int(ctx->depth_mods.size());
+  if (const int nt = int(ctx->texture_mods.size())) {
+    hipLaunchKernelGGL(texture_match_kernel, dim3(nt), dim3(M3T_TEXTURE_MATCH_THREADS), 0, ctx->stream,
+                       ctx->d_texture.as<TextureModDev>(), ctx->cams_active, ctx->d_poses.as<float>(),
+                       corr_iteration == 0 ? 1 : 0);
+    HIPCHK(hipGetLastError());
+  }
   if (nr) {
     hipLaunchKernelGGL(ctx->layout.off_hist >= 0 ? region_correspondence_lds_kernel : region_correspondence_kernel,
                        dim3(nr), dim3(M3T_BLOCK_THREADS), ctx->lds_corr, ctx->stream,
@@ -1764,6 +1834,11 @@ int LaunchCorrespondences(Ctx* ctx, int iteration, int corr_iteration) {
 
 int LaunchGradientHessian(Ctx* ctx, int corr_iteration, int opt_iteration) {
   int nr = int(ctx->region_mods.size()), nd = int(ctx->depth_mods.size());
+  if (const int nt = int(ctx->texture_mods.size())) {
+    hipLaunchKernelGGL(texture_gradient_hessian_kernel, dim3(nt), dim3(M3T_TEXTURE_MATCH_THREADS), 0, ctx->stream,
+                       ctx->d_texture.as<TextureModDev>(), ctx->cams_active, ctx->d_poses.as<float>(), corr_iteration);
+    HIPCHK(hipGetLastError());
+  }
   if (nr) {
     hipLaunchKernelGGL(region_gradient_hessian_kernel, dim3(nr), dim3(M3T_BLOCK_THREADS), ctx->lds_corr, ctx->stream,
                        ctx->d_region.as<RegionModDev>(), ctx->cams_active, ctx->d_poses.as<float>(),
@@ -1949,12 +2024,16 @@ int Prepare(Ctx* ctx, bool need_images) {
 }
 
 RegionMod* GetRegion(Ctx* ctx, int id) {
-  if (id < 0 || id >= int(ctx->modalities.size()) || !ctx->modalities[id].region) return nullptr;
+  if (id < 0 || id >= int(ctx->modalities.size()) || ctx->modalities[id].kind != kRegionModality) return nullptr;
   return ctx->region_mods[ctx->modalities[id].index].get();
 }
 DepthMod* GetDepth(Ctx* ctx, int id) {
-  if (id < 0 || id >= int(ctx->modalities.size()) || ctx->modalities[id].region) return nullptr;
+  if (id < 0 || id >= int(ctx->modalities.size()) || ctx->modalities[id].kind != kDepthModality) return nullptr;
   return ctx->depth_mods[ctx->modalities[id].index].get();
+}
+TextureMod* GetTexture(Ctx* ctx, int id) {
+  if (id < 0 || id >= int(ctx->modalities.size()) || ctx->modalities[id].kind != kTextureModality) return nullptr;
+  return ctx->texture_mods[ctx->modalities[id].index].get();
 }
 
 // ---- what the enqueued calls share (m3t_hip_reset_bodies, m3t_hip_reset_structures, m3t_hip_judge_bodies): validate ->
@@ -1993,6 +2072,15 @@ BodiesRead CollectReads(Ctx* ctx, const std::vector<char>& listed) {
   for (auto& m : ctx->depth_mods)
     if (listed[size_t(m->body)]) out.cameras.push_back(m->camera);
   return out;
+}
+// A reset restarts a body's modalities from the host's side of the boundary; a texture modality's restart needs the
+// caller's detector on the frame at the new pose (StartModality :315-322), which no enqueued call can run.
+int RefuseTextureBodies(Ctx* ctx, const std::vector<char>& listed, const char* entry) {
+  for (auto& m : ctx->texture_mods)
+    REQUIRE(!listed[size_t(m->body)], M3T_ERR_UNSUPPORTED,
+            std::string(entry) + ": a listed body has a texture modality (set the pose, set the features of the frame "
+            "and call start_modalities)");
+  return M3T_OK;
 }
 // Launches outside the fused step read the current frames of these cameras unguarded: outside the trackers' rectangle a
 // slot filled by ROI ingest holds whatever an earlier frame left there, and a body reset between two steps reads its
@@ -2497,6 +2585,7 @@ int m3t_hip_set_roi_ingest(m3t_hip_context* ctx, int enable, float margin_px) {
   CHECK_CTX();
   REQUIRE(margin_px >= 0.0f && margin_px < 1.0e6f, M3T_ERR_INVALID_ARGUMENT, "bad margin");
   REQUIRE(enable >= 0 && enable <= 2, M3T_ERR_INVALID_ARGUMENT, "enable: 0 (off), 1 (one margin for all bodies) or 2 (adaptive margins)");
+  REQUIRE(enable == 0 || ctx->texture_mods.empty(), M3T_ERR_UNSUPPORTED, "a texture modality and ROI ingest do not go together");
   if ((enable != 0) != ctx->roi_enabled) ctx->tables_dirty = true;
   ctx->roi_enabled = enable != 0;
   ctx->roi_adaptive = enable == 2;
@@ -2931,7 +3020,7 @@ int m3t_hip_region_modality_create(m3t_hip_context* ctx, const m3t_region_modali
   d.view_neighbors = mdl.view_neighbors.as<float4>();
   d.last_view = m->gh.as<int>() + 44;
   ctx->region_mods.push_back(std::move(m));
-  ctx->modalities.push_back({true, int(ctx->region_mods.size()) - 1});
+  ctx->modalities.push_back({kRegionModality, int(ctx->region_mods.size()) - 1});
   ctx->tables_dirty = true;
   return int(ctx->modalities.size()) - 1;
 }
@@ -2992,15 +3081,14 @@ int m3t_hip_depth_modality_create(m3t_hip_context* ctx, const m3t_depth_modality
   d.point_state = m->point_state.as<float>();
   d.gradient_hessian = m->gh.as<float>();
   ctx->depth_mods.push_back(std::move(m));
-  ctx->modalities.push_back({false, int(ctx->depth_mods.size()) - 1});
+  ctx->modalities.push_back({kDepthModality, int(ctx->depth_mods.size()) - 1});
   ctx->tables_dirty = true;
   return int(ctx->modalities.size()) - 1;
 }
 
 static float* ModalityGh(m3t_hip_context* ctx, int id) {
   if (id < 0 || id >= int(ctx->modalities.size())) return nullptr;
-  const ModalityRef& r = ctx->modalities[id];
-  return r.region ? ctx->region_mods[r.index]->gh.as<float>() : ctx->depth_mods[r.index]->gh.as<float>();
+  return ModalityGhPointer(ctx, ctx->modalities[id]);
 }
 int m3t_hip_modality_get_gradient_hessian(m3t_hip_context* ctx, int id, float g[6], float h[36]) {
   CHECK_CTX();
@@ -3375,7 +3463,7 @@ int m3t_hip_region_modality_use_region_checking(m3t_hip_context* ctx, int modali
 }
 int m3t_hip_depth_modality_model_occlusions(m3t_hip_context* ctx, int modality, int renderer) {
   CHECK_CTX();
-  REQUIRE(modality >= 0 && modality < int(ctx->modalities.size()) && !ctx->modalities[modality].region,
+  REQUIRE(modality >= 0 && modality < int(ctx->modalities.size()) && ctx->modalities[modality].kind == kDepthModality,
           M3T_ERR_INVALID_ARGUMENT, "bad depth modality id");
   DepthMod* m = ctx->depth_mods[ctx->modalities[modality].index].get();
   int r = CheckAttach(ctx, modality, renderer, false, false, m->body);
@@ -3391,7 +3479,7 @@ int m3t_hip_depth_modality_model_occlusions(m3t_hip_context* ctx, int modality, 
 }
 int m3t_hip_depth_modality_use_silhouette_checking(m3t_hip_context* ctx, int modality, int renderer) {
   CHECK_CTX();
-  REQUIRE(modality >= 0 && modality < int(ctx->modalities.size()) && !ctx->modalities[modality].region,
+  REQUIRE(modality >= 0 && modality < int(ctx->modalities.size()) && ctx->modalities[modality].kind == kDepthModality,
           M3T_ERR_INVALID_ARGUMENT, "bad depth modality id");
   DepthMod* m = ctx->depth_mods[ctx->modalities[modality].index].get();
   int r = CheckAttach(ctx, modality, renderer, false, true, m->body);
@@ -3401,6 +3489,191 @@ int m3t_hip_depth_modality_use_silhouette_checking(m3t_hip_context* ctx, int mod
   m->dev.use_silhouette_checking = 1;
   m->dev.body_id = ctx->body_geometries[m->body]->body_id;
   ctx->tables_dirty = true;
+  return M3T_OK;
+}
+
+// ---- TextureModality behind its feature detector (m3t_texture.hip) --------------------------------------------------
+int m3t_hip_texture_modality_create(m3t_hip_context* ctx, const m3t_texture_modality_params* p, int body, int color_camera,
+                                    int silhouette_renderer, int depth_camera) {
+  CHECK_CTX();
+  REQUIRE(p, M3T_ERR_INVALID_ARGUMENT, "null params");
+  REQUIRE(body >= 0 && body < int(ctx->body_poses.size() / 16), M3T_ERR_INVALID_ARGUMENT, "bad body id");
+  REQUIRE(color_camera >= 0 && color_camera < int(ctx->cameras.size()) && !ctx->cameras[color_camera]->is_depth,
+          M3T_ERR_INVALID_ARGUMENT, "bad color camera id");
+  if (p->measure_occlusions)
+    REQUIRE(depth_camera >= 0 && depth_camera < int(ctx->cameras.size()) && ctx->cameras[depth_camera]->is_depth,
+            M3T_ERR_INVALID_ARGUMENT, "measure_occlusions needs a depth camera");
+  REQUIRE(p->descriptor_bytes == 32 || p->descriptor_bytes == 64, M3T_ERR_INVALID_ARGUMENT,
+          "descriptor_bytes must be 32 (ORB) or 64 (BRISK, FREAK): Hamming-norm descriptors only");
+  REQUIRE(p->n_keyframes >= 1 && p->n_keyframes <= M3T_MAX_TEXTURE_KEYFRAMES && p->n_standard_deviations >= 1 &&
+              p->n_standard_deviations <= M3T_MAX_SCALES && p->focused_image_size >= 1,
+          M3T_ERR_INVALID_ARGUMENT, "bad texture modality parameters");
+  REQUIRE(silhouette_renderer >= 0 && silhouette_renderer < int(ctx->renderers.size()), M3T_ERR_INVALID_ARGUMENT,
+          "bad renderer id");
+  {
+    const RendererH& r = *ctx->renderers[silhouette_renderer];
+    // (the reference only warns, :59-63; with REGION ids the silhouette test of Reconstruct3DPoint matches nothing)
+    REQUIRE(r.silhouette && r.id_type == M3T_ID_TYPE_BODY, M3T_ERR_INVALID_ARGUMENT,
+            "the texture modality needs a focused silhouette renderer with id_type BODY");
+    REQUIRE(r.camera == color_camera, M3T_ERR_INVALID_ARGUMENT, "the silhouette renderer has to render the color camera's view");
+  }
+  int r = CheckAttach(ctx, -1, silhouette_renderer, false, true, body);
+  if (r) return r;
+  REQUIRE(HasGeometry(ctx, body), M3T_ERR_NOT_SET_UP, "the texture modality's body needs its geometry (body_set_geometry)");
+  REQUIRE(!ctx->roi_enabled, M3T_ERR_UNSUPPORTED, "a texture modality and ROI ingest do not go together");
+  REQUIRE(!ctx->Distributed(), M3T_ERR_UNSUPPORTED,
+          "a texture modality and a communicator / reduce callback do not go together");
+  HIPCHK(hipSetDevice(ctx->device));
+  auto m = std::make_unique<TextureMod>();
+  m->p = *p;
+  m->body = body;
+  m->camera = color_camera;
+  m->depth_camera = p->measure_occlusions ? depth_camera : -1;
+  m->silhouette_renderer = silhouette_renderer;
+  TextureModDev& d = m->dev;
+  d.body = body;
+  d.camera = color_camera;
+  d.depth_camera = m->depth_camera;
+  d.descriptor_words = p->descriptor_bytes / 4;
+  d.n_keyframes_max = p->n_keyframes;
+  d.descriptor_distance_threshold = p->descriptor_distance_threshold;
+  d.tukey_norm_constant = p->tukey_norm_constant;
+  d.n_standard_deviations = p->n_standard_deviations;
+  for (int i = 0; i < M3T_MAX_SCALES; ++i) d.standard_deviations[i] = p->standard_deviations[i];
+  d.max_keyframe_rotation_difference = p->max_keyframe_rotation_difference;
+  d.max_keyframe_age = p->max_keyframe_age;
+  d.measure_occlusions = p->measure_occlusions ? 1 : 0;
+  d.measured_occlusion_radius = p->measured_occlusion_radius;
+  d.measured_occlusion_threshold = p->measured_occlusion_threshold;
+  d.model_occlusions = 0;
+  d.body_id = ctx->body_geometries[body]->body_id;
+  d.modeled_occlusion_radius = p->modeled_occlusion_radius;
+  d.modeled_occlusion_threshold = p->modeled_occlusion_threshold;
+  const size_t words = size_t(d.descriptor_words), slots = size_t(p->n_keyframes) * M3T_TEXTURE_MAX_FEATURES;
+  HIPCHK(m->features.alloc((TF_HEADER_WORDS + (2 + words) * M3T_TEXTURE_MAX_FEATURES) * 4));
+  HIPCHK(m->keyframe_points.alloc(slots * 3 * 4));
+  HIPCHK(m->keyframe_descriptors.alloc(slots * words * 4));
+  HIPCHK(m->data_points.alloc(slots * TP_FLOATS * 4));
+  HIPCHK(m->state.alloc(sizeof(TextureStateDev)));
+  HIPCHK(m->gh.alloc(42 * 4));
+  HIPCHK(hipMemset(m->features.p, 0, TF_HEADER_WORDS * 4));
+  HIPCHK(hipMemset(m->state.p, 0, m->state.bytes));
+  HIPCHK(hipMemset(m->gh.p, 0, m->gh.bytes));
+  d.features = m->features.as<uint32_t>();
+  d.keyframe_points = m->keyframe_points.as<float>();
+  d.keyframe_descriptors = m->keyframe_descriptors.as<uint32_t>();
+  d.data_points = m->data_points.as<float>();
+  d.state = m->state.as<TextureStateDev>();
+  d.gradient_hessian = m->gh.as<float>();
+  ctx->texture_mods.push_back(std::move(m));
+  ctx->modalities.push_back({kTextureModality, int(ctx->texture_mods.size()) - 1});
+  ctx->tables_dirty = true;
+  return int(ctx->modalities.size()) - 1;
+}
+int m3t_hip_texture_modality_model_occlusions(m3t_hip_context* ctx, int modality, int renderer) {
+  CHECK_CTX();
+  TextureMod* m = GetTexture(ctx, modality);
+  REQUIRE(m, M3T_ERR_INVALID_ARGUMENT, "bad texture modality id");
+  int r = CheckAttach(ctx, modality, renderer, false, false, m->body);
+  if (r) return r;
+  REQUIRE(ctx->renderers[renderer]->camera == m->camera, M3T_ERR_INVALID_ARGUMENT,
+          "the depth renderer has to render the color camera's view");
+  m->depth_renderer = renderer;
+  m->dev.model_occlusions = 1;
+  ctx->tables_dirty = true;
+  return M3T_OK;
+}
+int m3t_hip_texture_modality_get_region_of_interest(m3t_hip_context* ctx, int modality, int roi[4], float* scale, int* valid) {
+  CHECK_CTX();
+  TextureMod* m = GetTexture(ctx, modality);
+  REQUIRE(m, M3T_ERR_INVALID_ARGUMENT, "bad texture modality id");
+  REQUIRE(roi && scale && valid, M3T_ERR_INVALID_ARGUMENT, "null output");
+  float pose[16];
+  int r = m3t_hip_body_get_body2world_pose(ctx, m->body, pose);  // (waits for the stream when the device is ahead)
+  if (r) return r;
+  const Camera& c = *ctx->cameras[m->camera];
+  // translation of world2camera * body2world: L t + t_camera, Transform * Transform as the kernels form it (mul_pose)
+  const float* w = c.world2camera;
+  float t[3];
+  for (int k = 0; k < 3; ++k) t[k] = ((w[k] * pose[12] + w[4 + k] * pose[13]) + w[8 + k] * pose[14]) + w[12 + k];
+  const float radius = 0.5f * ctx->body_geometries[m->body]->maximum_body_diameter;
+  *valid = m3t_tex_region_of_interest(t, radius, c.intr.fu, c.intr.fv, c.intr.ppu, c.intr.ppv, c.intr.width, c.intr.height,
+                                      m->p.focused_image_size, roi, scale)
+               ? 1
+               : 0;
+  return M3T_OK;
+}
+int m3t_hip_texture_modality_set_features(m3t_hip_context* ctx, int modality, const float* keypoints_xy,
+                                          const uint8_t* descriptors, int n) {
+  CHECK_CTX();
+  TextureMod* m = GetTexture(ctx, modality);
+  REQUIRE(m, M3T_ERR_INVALID_ARGUMENT, "bad texture modality id");
+  REQUIRE(n >= 0 && n <= M3T_MAX_TEXTURE_FEATURES, M3T_ERR_INVALID_ARGUMENT,
+          "set_features: n must be in [0, " + std::to_string(M3T_MAX_TEXTURE_FEATURES) + "]");
+  REQUIRE(n == 0 || (keypoints_xy && descriptors), M3T_ERR_INVALID_ARGUMENT, "set_features: null features");
+  HIPCHK(hipSetDevice(ctx->device));
+  // one block: {n, 0, 0, 0} | keypoints | descriptors; two copies on the context's stream, behind whatever it holds
+  const size_t head_bytes = TF_HEADER_WORDS * 4 + size_t(n) * 8, descriptor_bytes = size_t(n) * m->p.descriptor_bytes;
+  void *host = nullptr, *dev = nullptr;
+  int slot = 0;
+  HIPCHK(m->uploads.Acquire(head_bytes + descriptor_bytes, &host, &dev, &slot));
+  uint8_t* block = static_cast<uint8_t*>(host);
+  const uint32_t header[TF_HEADER_WORDS] = {uint32_t(n), 0u, 0u, 0u};
+  std::memcpy(block, header, sizeof(header));
+  if (n) {
+    std::memcpy(block + sizeof(header), keypoints_xy, size_t(n) * 8);
+    std::memcpy(block + head_bytes, descriptors, descriptor_bytes);
+  }
+  uint8_t* target = m->features.as<uint8_t>();
+  HIPCHK(hipMemcpyAsync(target, block, head_bytes, hipMemcpyHostToDevice, ctx->stream));
+  if (n)
+    HIPCHK(hipMemcpyAsync(target + (TF_HEADER_WORDS + 2 * M3T_TEXTURE_MAX_FEATURES) * 4, block + head_bytes, descriptor_bytes,
+                          hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(m->uploads.Release(slot, ctx->stream));
+  if (ctx->async_ingest) ctx->untracked_launches = true;
+  return M3T_OK;
+}
+int m3t_hip_texture_modality_get_points(m3t_hip_context* ctx, int modality, m3t_texture_data_point* out, int capacity,
+                                        int* n_points) {
+  CHECK_CTX();
+  TextureMod* m = GetTexture(ctx, modality);
+  REQUIRE(m, M3T_ERR_INVALID_ARGUMENT, "bad texture modality id");
+  REQUIRE(n_points && capacity >= 0 && (out || capacity == 0), M3T_ERR_INVALID_ARGUMENT, "bad output buffer");
+  static_assert(sizeof(m3t_texture_data_point) == TP_FLOATS * 4, "the kernels write m3t_texture_data_point rows");
+  HIPCHK(hipSetDevice(ctx->device));
+  TextureStateDev st;
+  HIPCHK(hipMemcpyAsync(&st, m->state.p, sizeof(st), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  *n_points = st.n_data_points;
+  const int n = std::min(st.n_data_points, capacity);
+  if (n > 0) HIPCHK(hipMemcpy(out, m->data_points.p, size_t(n) * sizeof(m3t_texture_data_point), hipMemcpyDeviceToHost));
+  return M3T_OK;
+}
+int m3t_hip_texture_modality_get_keyframes(m3t_hip_context* ctx, int modality, int* n_keyframes, int* keyframe_age,
+                                           int* counts, float* points_xyz, int capacity_points) {
+  CHECK_CTX();
+  TextureMod* m = GetTexture(ctx, modality);
+  REQUIRE(m, M3T_ERR_INVALID_ARGUMENT, "bad texture modality id");
+  HIPCHK(hipSetDevice(ctx->device));
+  TextureStateDev st;
+  HIPCHK(hipMemcpyAsync(&st, m->state.p, sizeof(st), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  int total = 0;
+  for (int k = 0; k < st.n_keyframes; ++k) total += st.counts[(st.head + k) % m->p.n_keyframes];
+  REQUIRE(!points_xyz || capacity_points >= total, M3T_ERR_INVALID_ARGUMENT,
+          "get_keyframes: the keyframes hold " + std::to_string(total) + " points");
+  if (n_keyframes) *n_keyframes = st.n_keyframes;
+  if (keyframe_age) *keyframe_age = st.keyframe_age;
+  size_t at = 0;
+  for (int k = 0; k < M3T_MAX_TEXTURE_KEYFRAMES; ++k) {
+    const int slot = (st.head + k) % m->p.n_keyframes;
+    const int count = k < st.n_keyframes ? st.counts[slot] : 0;
+    if (counts) counts[k] = count;
+    if (points_xyz && count > 0)
+      HIPCHK(hipMemcpy(points_xyz + at * 3, m->keyframe_points.as<float>() + size_t(slot) * M3T_TEXTURE_MAX_FEATURES * 3,
+                       size_t(count) * 12, hipMemcpyDeviceToHost));
+    at += size_t(count);
+  }
   return M3T_OK;
 }
 
@@ -3691,7 +3964,7 @@ int m3t_hip_link_add_modality(m3t_hip_context* ctx, int link, int modality) {
   REQUIRE(link >= 0 && link < int(ctx->links.size()) && modality >= 0 && modality < int(ctx->modalities.size()),
           M3T_ERR_INVALID_ARGUMENT, "bad ids");
   const ModalityRef& ref = ctx->modalities[modality];
-  int mbody = ref.region ? ctx->region_mods[ref.index]->body : ctx->depth_mods[ref.index]->body;
+  int mbody = ModalityBody(ctx, ref);
   REQUIRE(mbody == ctx->links[link].body, M3T_ERR_INVALID_ARGUMENT, "modality and link refer to different bodies");
   ctx->links[link].modalities.push_back(modality);
   ctx->tables_dirty = true;
@@ -3899,6 +4172,7 @@ int m3t_hip_start_modalities(m3t_hip_context* ctx, int iteration) {
     *static_cast<volatile unsigned*>(ctx->table_overflow_host) = 0u;
   }
   if ((r = RenderForModalities(ctx, true))) return r;  // start_modality_renderer_ptrs tracker.cpp:430-436
+  if ((r = LaunchTextureKeyframes(ctx, false))) return r;
   return LaunchHistogram(ctx, iteration, true);
 }
 // RBOTEvaluator::ResetBody (rbot_evaluator.cpp:334-342) for n bodies of the batch: their poses, the start-modality
@@ -3916,6 +4190,7 @@ int m3t_hip_reset_bodies(m3t_hip_context* ctx, const int* body_ids, const float*
     REQUIRE(l.body < 0 || !listed[l.body] || (l.parent < 0 && l.children.empty()), M3T_ERR_UNSUPPORTED,
             "reset_bodies: a listed body belongs to a structure of more than one link (set the poses of the "
             "structure and call start_modalities)");
+  if ((r = RefuseTextureBodies(ctx, listed, "reset_bodies"))) return r;
   const BodiesRead reads = CollectReads(ctx, listed);
   REQUIRE(reads.shared_ids.empty(), M3T_ERR_UNSUPPORTED,
           "reset_bodies: a region modality of a listed body uses shared ColorHistograms (call start_modalities)");
@@ -4006,6 +4281,7 @@ int m3t_hip_reset_structures(m3t_hip_context* ctx, const int* optimizer_ids, int
       entries.push_back(e);
     }
   }
+  if ((r = RefuseTextureBodies(ctx, listed, "reset_structures"))) return r;
   const BodiesRead reads = CollectReads(ctx, listed);
   for (auto& m : ctx->region_mods)
     REQUIRE(m->shared_histograms < 0 || listed[size_t(m->body)] ||
@@ -4209,6 +4485,7 @@ int m3t_hip_judge_bodies(m3t_hip_context* ctx, int judge, const float* gt_body2w
       REQUIRE(l.body < 0 || !listed[size_t(l.body)] || (l.parent < 0 && l.children.empty()), M3T_ERR_UNSUPPORTED,
               "judge_bodies: a listed body belongs to a structure of more than one link (judge with "
               "reset_iteration < 0 and reset the structure from the host)");
+    if ((r = RefuseTextureBodies(ctx, listed, "judge_bodies"))) return r;
     reads = CollectReads(ctx, listed);
     std::vector<std::vector<int>> of_body(static_cast<size_t>(n));
     for (int id : reads.region_ids) {
@@ -4596,6 +4873,7 @@ int m3t_hip_comm_init_rank(m3t_hip_context* ctx, const void* id, size_t bytes, i
   CHECK_CTX();
   REQUIRE(id && bytes >= sizeof(ncclUniqueId) && n_ranks >= 1 && rank >= 0 && rank < n_ranks, M3T_ERR_INVALID_ARGUMENT,
           "bad communicator description");
+  REQUIRE(ctx->texture_mods.empty(), M3T_ERR_UNSUPPORTED, "a texture modality and a communicator / reduce callback do not go together");
   REQUIRE(g_rccl.Load(), M3T_ERR_DEVICE, g_rccl.error);
   HIPCHK(hipSetDevice(ctx->device));
   if (ctx->comm && ctx->comm_owned) RCCLCHK(g_rccl.CommDestroy(ctx->comm));
@@ -4612,6 +4890,7 @@ int m3t_hip_comm_init_rank(m3t_hip_context* ctx, const void* id, size_t bytes, i
 }
 int m3t_hip_comm_set(m3t_hip_context* ctx, void* nccl_comm) {
   CHECK_CTX();
+  REQUIRE(nccl_comm == nullptr || ctx->texture_mods.empty(), M3T_ERR_UNSUPPORTED, "a texture modality and a communicator / reduce callback do not go together");
   REQUIRE(nccl_comm == nullptr || g_rccl.Load(), M3T_ERR_DEVICE, g_rccl.error);
   if (ctx->comm && ctx->comm_owned) RCCLCHK(g_rccl.CommDestroy(ctx->comm));
   ctx->comm = static_cast<ncclComm_t>(nccl_comm);
@@ -4634,6 +4913,7 @@ int m3t_hip_comm_destroy(m3t_hip_context* ctx) {
 // as with a communicator.  NULL takes it out again.
 int m3t_hip_comm_set_reduce_callback(m3t_hip_context* ctx, m3t_hip_reduce_fn fn, void* user) {
   CHECK_CTX();
+  REQUIRE(fn == nullptr || ctx->texture_mods.empty(), M3T_ERR_UNSUPPORTED, "a texture modality and a communicator / reduce callback do not go together");
   ctx->reduce_fn = fn;
   ctx->reduce_user = fn ? user : nullptr;
   return M3T_OK;
@@ -4662,6 +4942,7 @@ int m3t_hip_calculate_results(m3t_hip_context* ctx, int iteration) {
   r = Prepare(ctx, true);
   if (r) return r;
   if ((r = RenderForModalities(ctx, true))) return r;  // results_renderer_ptrs tracker.cpp:503-509
+  if ((r = LaunchTextureKeyframes(ctx, true))) return r;
   return LaunchHistogram(ctx, iteration, false);
 }
 
@@ -5143,6 +5424,7 @@ int m3t_hip_execute_tracking_step(m3t_hip_context* ctx, int iteration) {
   if (r) return r;
   if (!report.histogram_fused) {
     if ((r = RenderForModalities(ctx, true))) return r;
+    if ((r = LaunchTextureKeyframes(ctx, true))) return r;
     if ((r = LaunchHistogram(ctx, iteration, false, roi_frames))) return r;
   }
   if (roi_active) {  // the poses the step ends on = the poses the next one starts from

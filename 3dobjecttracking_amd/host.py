@@ -17,8 +17,9 @@ import sys
 import numpy as np
 
 from . import _capi
-from ._capi import (DATA_LINE_DTYPE, DATA_POINT_DTYPE, DepthModalityParams, DepthModelDesc, Intrinsics, M3TError,
-                    RegionModalityParams, RegionModelDesc, fptr, iptr, pose_arg, pose_ret)
+from ._capi import (DATA_LINE_DTYPE, DATA_POINT_DTYPE, M3T_MAX_TEXTURE_FEATURES, M3T_MAX_TEXTURE_KEYFRAMES,
+                    TEXTURE_DATA_POINT_DTYPE, DepthModalityParams, DepthModelDesc, Intrinsics, M3TError,
+                    RegionModalityParams, RegionModelDesc, TextureModalityParams, fptr, iptr, pose_arg, pose_ret)
 
 
 class Tracker:
@@ -561,6 +562,71 @@ class DepthModality(_Modality):
         out = np.zeros(cap, DATA_POINT_DTYPE)
         self.api.call("depth_modality_get_points", self.id, out.ctypes.data_as(C.c_void_p), cap, C.byref(n))
         return out[:min(n.value, cap)]
+
+
+class TextureModality(_Modality):
+    """TextureModality behind its feature detector (texture_modality.cpp): the caller detects and describes features in
+    the focused image of RegionOfInterest() and hands them over with SetFocusedFeatures (or SetFeatures, in full-image
+    coordinates); keyframes, matching, g/H and keyframe renewal run on the device."""
+
+    def __init__(self, api, body, color_camera, silhouette_renderer, depth_camera=None, params=None, **kw):
+        self.api = api
+        self.params = params if params is not None else TextureModalityParams(**kw)
+        self.id = api.call("texture_modality_create", C.byref(self.params), body.id, color_camera.id,
+                           silhouette_renderer.id, depth_camera.id if depth_camera is not None else -1)
+
+    def ModelOcclusions(self, depth_renderer):
+        self.api.call("texture_modality_model_occlusions", self.id, depth_renderer.id)
+
+    def RegionOfInterest(self):
+        """CalculateScaleAndRegionOfInterest at the body's current pose: ((x, y, width, height), scale), or None where
+        the reference returns false (then SetFeatures with no features)"""
+        roi = np.zeros(4, np.int32)
+        scale = np.zeros(1, np.float32)
+        valid = C.c_int()
+        self.api.call("texture_modality_get_region_of_interest", self.id, iptr(roi), fptr(scale), C.byref(valid))
+        return ((int(roi[0]), int(roi[1]), int(roi[2]), int(roi[3])), np.float32(scale[0])) if valid.value else None
+
+    def SetFeatures(self, keypoints, descriptors):
+        """keypoints: n x 2 in full-image coordinates; descriptors: n rows of descriptor_bytes"""
+        keypoints = np.ascontiguousarray(keypoints, np.float32).reshape(-1, 2)
+        descriptors = np.ascontiguousarray(descriptors, np.uint8).reshape(len(keypoints), self.params.descriptor_bytes) \
+            if len(keypoints) == 0 else np.ascontiguousarray(descriptors, np.uint8).reshape(len(keypoints), -1)
+        if len(keypoints) and descriptors.shape[1] != self.params.descriptor_bytes:
+            raise ValueError("descriptors must have %d bytes per row" % self.params.descriptor_bytes)
+        self.api.call("texture_modality_set_features", self.id, fptr(keypoints),
+                      descriptors.ctypes.data_as(C.POINTER(C.c_uint8)), len(keypoints))
+
+    def SetFocusedFeatures(self, roi, scale, focused_keypoints, descriptors):
+        """keypoints of the focused image: pt = roi.x + pt.x / scale in f32 (texture_modality.cpp:884-887)"""
+        pts = np.asarray(focused_keypoints, np.float32).reshape(-1, 2)
+        scale = np.float32(scale)
+        full = np.empty_like(pts)
+        full[:, 0] = np.float32(roi[0]) + pts[:, 0] / scale
+        full[:, 1] = np.float32(roi[1]) + pts[:, 1] / scale
+        self.SetFeatures(full, descriptors)
+
+    def points(self):
+        """data_points_ of the last CalculateCorrespondences / CalculateGradientAndHessian"""
+        cap = self.params.n_keyframes * M3T_MAX_TEXTURE_FEATURES
+        n = C.c_int()
+        self.api.call("texture_modality_get_points", self.id, None, 0, C.byref(n))
+        out = np.zeros(min(n.value, cap), TEXTURE_DATA_POINT_DTYPE)
+        if len(out):
+            self.api.call("texture_modality_get_points", self.id, out.ctypes.data_as(C.c_void_p), len(out), C.byref(n))
+        return out[:min(n.value, len(out))]
+
+    def keyframes(self):
+        """(keyframe_age, [points of the oldest keyframe (k x 3), ..., of the newest])"""
+        nk, age = C.c_int(), C.c_int()
+        counts = np.zeros(M3T_MAX_TEXTURE_KEYFRAMES, np.int32)
+        self.api.call("texture_modality_get_keyframes", self.id, C.byref(nk), C.byref(age), iptr(counts), None, 0)
+        total = int(counts.sum())
+        xyz = np.zeros((max(total, 1), 3), np.float32)
+        self.api.call("texture_modality_get_keyframes", self.id, C.byref(nk), C.byref(age), iptr(counts), fptr(xyz),
+                      len(xyz))
+        edges = np.concatenate([[0], np.cumsum(counts[:nk.value])])
+        return age.value, [xyz[edges[k]:edges[k + 1]].copy() for k in range(nk.value)]
 
 
 class Link:

@@ -241,6 +241,48 @@ int m3t_hip_region_modality_use_region_checking(m3t_hip_context*, int modality_i
 int m3t_hip_depth_modality_model_occlusions(m3t_hip_context*, int modality_id, int depth_renderer_id);
 int m3t_hip_depth_modality_use_silhouette_checking(m3t_hip_context*, int modality_id, int silhouette_renderer_id);
 
+/* ---- TextureModality behind its feature detector (texture_modality.cpp; line numbers below are that file's) ----------
+ * Detection and description stay with the caller, as the reference delegates them to OpenCV (:858-888); everything
+ * behind them runs on the device: keyframe reconstruction through the focused silhouette renderer with the two
+ * occlusion tests (ComputeKeyframeData :933-1127), the brute-force 2-nearest-neighbour Hamming match with the ratio test
+ * and the projection (CalculateCorrespondences :324-387), the Tukey-weighted g/H (:397-444, sums in the reference's
+ * sequential order) and the keyframe renewal (CalculateResults :456-472, decided on the device).  Only Hamming-norm
+ * descriptors: ORB (32 bytes), BRISK and FREAK (64 bytes).
+ * texture_modality_create: the renderer has to be a focused SILHOUETTE renderer with id_type BODY that references the
+ *   body (refused otherwise: the reference only warns, :59-63, and then matches nothing); depth_camera_id = -1 unless
+ *   measure_occlusions.  The body needs its geometry (body_set_geometry: the region of interest uses its diameter).
+ * texture_modality_model_occlusions: TextureModality::ModelOcclusions with the focused depth renderer named.
+ * texture_modality_get_region_of_interest: CalculateScaleAndRegionOfInterest (:890-931) at the body's current pose:
+ *   roi = {x, y, width, height}, *valid = 0 where the reference returns false (roi and scale are then untouched).  It
+ *   reads the pose back, so it waits for the stream: the caller's detector boundary.
+ * texture_modality_set_features: keypoints_ in full-image coordinates (n x 2 floats) and descriptors_ (n rows of
+ *   descriptor_bytes).  n in [0, 4096], more is M3T_ERR_INVALID_ARGUMENT before anything changes; n = 0 says "the
+ *   region of interest was not valid" and leaves no features (the reference clears the keypoints and keeps stale
+ *   descriptors there, :865).  The upload is enqueued through a small ring of page-locked blocks: a step that is still
+ *   running keeps the features it started with.
+ * The matcher's contract: for every keyframe descriptor, in order, the two current descriptors of smallest Hamming
+ *   distance, the LOWER index first among equal distances (cv::BFMatcher::knnMatch(k = 2)); fewer than two current
+ *   descriptors: no match; a query is kept iff NOT float(d0) / float(d1) >= descriptor_distance_threshold in f32 (0 / 0
+ *   is NaN and kept, as in the reference).  Data points: keyframe after keyframe, query after query.
+ * texture_modality_get_points: data_points_ of the last CalculateCorrespondences / CalculateGradientAndHessian.
+ * texture_modality_get_keyframes: how many keyframes are held, keyframe_age_, the points per keyframe (oldest first;
+ *   8 ints) and, unless points_xyz is NULL, the points themselves, keyframe after keyframe (capacity_points x 3 floats;
+ *   M3T_ERR_INVALID_ARGUMENT if they do not fit).
+ * A context that holds a texture modality runs one launch per sub-step (get_step_kernel reports ""); reset_bodies,
+ * reset_structures and a resetting judge_bodies on a body with a texture modality, ROI ingest, and a communicator or
+ * reduce callback are M3T_ERR_UNSUPPORTED there. */
+int m3t_hip_texture_modality_create(m3t_hip_context*, const m3t_texture_modality_params*, int body_id, int color_camera_id,
+                                    int silhouette_renderer_id, int depth_camera_id);
+int m3t_hip_texture_modality_model_occlusions(m3t_hip_context*, int modality_id, int depth_renderer_id);
+int m3t_hip_texture_modality_get_region_of_interest(m3t_hip_context*, int modality_id, int roi[4], float* scale,
+                                                    int* valid);
+int m3t_hip_texture_modality_set_features(m3t_hip_context*, int modality_id, const float* keypoints_xy,
+                                          const uint8_t* descriptors, int n);
+int m3t_hip_texture_modality_get_points(m3t_hip_context*, int modality_id, m3t_texture_data_point* out, int capacity,
+                                        int* n_points);
+int m3t_hip_texture_modality_get_keyframes(m3t_hip_context*, int modality_id, int* n_keyframes, int* keyframe_age,
+                                           int* counts, float* points_xyz, int capacity_points);
+
 /* ColorHistograms shared by several RegionModalities (color_histograms.h:36-40, RegionModality::UseSharedColorHistograms
  * region_modality.cpp:168-173; cleared / initialised / updated once per step around all modalities, tracker.cpp:435-443,
  * 507-515).  The modality's own n_histogram_bins and learning rates are ignored once it shares. */

@@ -322,6 +322,54 @@ class DepthModality : public Modality {
     return out;
   }
 };
+// TextureModality behind its feature detector: the caller detects and describes features in the focused image of
+// RegionOfInterest() and hands them over in full-image coordinates (texture_modality.cpp:858-888)
+class TextureModality : public Modality {
+ public:
+  TextureModality(ContextPtr c, const Body& body, const ColorCamera& color_camera,
+                  const FocusedSilhouetteRenderer& silhouette_renderer, const m3t_texture_modality_params& params,
+                  const DepthCamera* depth_camera = nullptr) {
+    c_ = std::move(c);
+    id_ = c_->Check(m3t_hip_texture_modality_create(c_->get(), &params, body.id(), color_camera.id(),
+                                                    silhouette_renderer.id(), depth_camera ? depth_camera->id() : -1),
+                    "TextureModality");
+  }
+  bool ModelOcclusions(const FocusedBasicDepthRenderer& renderer) {
+    return c_->Step(m3t_hip_texture_modality_model_occlusions(c_->get(), id_, renderer.id()));
+  }
+  // roi = {x, y, width, height}; false where CalculateScaleAndRegionOfInterest returns false
+  bool RegionOfInterest(int roi[4], float* scale) const {
+    int valid = 0;
+    c_->Check(m3t_hip_texture_modality_get_region_of_interest(c_->get(), id_, roi, scale, &valid), "RegionOfInterest");
+    return valid != 0;
+  }
+  // n keypoints (x, y) in full-image coordinates, n rows of descriptor_bytes
+  bool SetFeatures(const float* keypoints_xy, const uint8_t* descriptors, int n) {
+    return c_->Step(m3t_hip_texture_modality_set_features(c_->get(), id_, keypoints_xy, descriptors, n));
+  }
+  std::vector<m3t_texture_data_point> data_points() const {
+    int n = 0;
+    c_->Check(m3t_hip_texture_modality_get_points(c_->get(), id_, nullptr, 0, &n), "data_points");
+    std::vector<m3t_texture_data_point> out(n);
+    if (n > 0) c_->Check(m3t_hip_texture_modality_get_points(c_->get(), id_, out.data(), n, &n), "data_points");
+    return out;
+  }
+  // points of the keyframes held, oldest first (xyz); counts: points per keyframe
+  std::vector<float> keyframes(std::vector<int>* counts = nullptr, int* keyframe_age = nullptr) const {
+    int n_keyframes = 0, per_keyframe[M3T_MAX_TEXTURE_KEYFRAMES] = {0};
+    c_->Check(m3t_hip_texture_modality_get_keyframes(c_->get(), id_, &n_keyframes, keyframe_age, per_keyframe, nullptr, 0),
+              "keyframes");
+    int total = 0;
+    for (int k = 0; k < n_keyframes; ++k) total += per_keyframe[k];
+    std::vector<float> xyz(size_t(total) * 3 + 3);
+    c_->Check(m3t_hip_texture_modality_get_keyframes(c_->get(), id_, &n_keyframes, keyframe_age, per_keyframe, xyz.data(),
+                                                     total),
+              "keyframes");
+    xyz.resize(size_t(total) * 3);
+    if (counts) counts->assign(per_keyframe, per_keyframe + n_keyframes);
+    return xyz;
+  }
+};
 
 // m3t::Optimizer with one free 6-dof root Link holding the modalities of one body
 class Optimizer {

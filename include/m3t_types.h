@@ -6,6 +6,7 @@
  * m3t::RegionModality / m3t::DepthModality / m3t::Optimizer instance:
  *   m3t_region_modality_params  <- M3T/include/m3t/region_modality.h:411-443
  *   m3t_depth_modality_params   <- M3T/include/m3t/depth_modality.h:302-321
+ *   m3t_texture_modality_params <- M3T/include/m3t/texture_modality.h:400-407, 431-436
  *   m3t_intrinsics              <- M3T/include/m3t/common.h (struct Intrinsics)
  *   m3t_region_model_desc       <- M3T/include/m3t/region_model.h:89-110 (+ model.h)
  *   m3t_depth_model_desc        <- M3T/include/m3t/depth_model.h:67-86
@@ -32,6 +33,8 @@ extern "C" {
 #define M3T_MAX_N_OCCLUSION_STRIDES 5 /* kMaxNOcclusionStrides, region_modality.h:145 */
 #define M3T_N_REGION_STRIDE 5          /* kNRegionStride, region_modality.h:146 */
 #define M3T_REGION_OFFSET 2.0f         /* kRegionOffset, region_modality.h:147 */
+#define M3T_MAX_TEXTURE_FEATURES 4096  /* features per m3t_hip_texture_modality_set_features call */
+#define M3T_MAX_TEXTURE_KEYFRAMES 8    /* cap of n_keyframes */
 
 /* status codes (the reference returns bool + std::cerr; 0 == true) */
 enum {
@@ -133,6 +136,26 @@ typedef struct m3t_depth_modality_params {
   float modeled_occlusion_threshold;
 } m3t_depth_modality_params;
 
+/* TextureModality behind its feature detector (texture_modality.h:400-407, 431-436).  Detection stays with the caller
+ * (the reference delegates it to one of five OpenCV classes); descriptors are Hamming-norm bit strings: ORB 32 bytes,
+ * BRISK and FREAK 64 bytes. */
+typedef struct m3t_texture_modality_params {
+  int descriptor_bytes; /* 32 or 64 */
+  int focused_image_size;
+  float descriptor_distance_threshold;
+  float tukey_norm_constant;
+  int n_standard_deviations;
+  float standard_deviations[M3T_MAX_SCALES];
+  float max_keyframe_rotation_difference; /* rad */
+  int max_keyframe_age;
+  int n_keyframes; /* 1 .. M3T_MAX_TEXTURE_KEYFRAMES */
+  int measure_occlusions;
+  float measured_occlusion_radius;
+  float measured_occlusion_threshold;
+  float modeled_occlusion_radius;   /* used once *_texture_modality_model_occlusions() names the renderer */
+  float modeled_occlusion_threshold;
+} m3t_texture_modality_params;
+
 /* Body geometry for the renderer-fed branches (body.h:46-60, body.cpp:196-250): a triangle mesh in
  * metres (geometry_unit_in_meter already applied), its pose in the body frame and the two ids the
  * silhouette renderer writes (body.h: body_id / region_id). */
@@ -187,6 +210,14 @@ typedef struct m3t_data_point {
   int valid;
   int model_point_index;
 } m3t_data_point;
+
+/* TextureModality::DataPoint (texture_modality.h:112-117) */
+typedef struct m3t_texture_data_point {
+  float center_f_body[3];
+  float center_f_camera[3];
+  float center[2];
+  float correspondence_center[2];
+} m3t_texture_data_point;
 
 /* One body's judgement by m3t_hip_judge_bodies: RBOTEvaluator::CalculatePoseResults (rbot_evaluator.cpp:416-433) and
  * YCBEvaluator::CalculatePoseResults (ycb_evaluator.cpp:803-848).  32 bytes. */
@@ -280,6 +311,26 @@ static inline void m3t_depth_modality_params_default(m3t_depth_modality_params* 
   p->n_unoccluded_iterations = 10;
   p->min_n_unoccluded_points = 0;
   p->modeled_depth_offset_radius = 0.01f;
+  p->modeled_occlusion_radius = 0.01f;
+  p->modeled_occlusion_threshold = 0.03f;
+}
+
+static inline void m3t_texture_modality_params_default(m3t_texture_modality_params* p) {
+  int i;
+  p->descriptor_bytes = 32; /* ORB, the reference's default descriptor type */
+  p->focused_image_size = 200;
+  p->descriptor_distance_threshold = 0.7f;
+  p->tukey_norm_constant = 20.0f;
+  p->n_standard_deviations = 2;
+  for (i = 0; i < M3T_MAX_SCALES; ++i) p->standard_deviations[i] = 0.0f;
+  p->standard_deviations[0] = 15.0f;
+  p->standard_deviations[1] = 5.0f;
+  p->max_keyframe_rotation_difference = 10.0f * 3.14159265358979323846f / 180.0f;
+  p->max_keyframe_age = 100;
+  p->n_keyframes = 1;
+  p->measure_occlusions = 0;
+  p->measured_occlusion_radius = 0.01f;
+  p->measured_occlusion_threshold = 0.03f;
   p->modeled_occlusion_radius = 0.01f;
   p->modeled_occlusion_threshold = 0.03f;
 }
