@@ -25,6 +25,7 @@
 #include "m3t_view_rows.h"
 #include "m3t_step_plan.h"
 #include "m3t_call_args.h"
+#include "m3t_ingest_plan.h"
 #include "m3t_kernels.hip"
 #include "m3t_judge.hip"
 #include "m3t_opt.hip"
@@ -133,6 +134,13 @@ struct Camera {
   uint8_t* frames = nullptr;      // slot 0 of this camera
   size_t slot_stride = 0;         // bytes from one slot of this camera to the next
   uint8_t* frame(int slot) const { return frames + size_t(slot) * slot_stride; }
+  void SetSlots(int n) {  // a new ring: no frames in it, no readers
+    n_slots = n;
+    current = 0;
+    has_image.assign(size_t(n), false);
+    last_read_step.assign(size_t(n), -1);
+    slot_is_roi.assign(size_t(n), false);
+  }
 };
 struct FrameSlab {  // the frame rings of a group of cameras of equal geometry in one allocation
   DevMem mem;
@@ -142,6 +150,130 @@ struct FrameSlab {  // the frame rings of a group of cameras of equal geometry i
   std::vector<hipEvent_t> slot_copied;
   ~FrameSlab() {
     for (auto& e : slot_copied)
+      if (e) (void)hipEventDestroy(e);
+  }
+};
+
+// A stream of the context.  With CUs reserved for ingest (m3t_hip_reserve_ingest_cus) the compute stream runs on the
+// CUs of mask bits [0, CUs - n) and copy stream 0 -- the one the ROI pull kernel is launched on -- on bits
+// [CUs - n, CUs).  Bit i of a mask belongs to XCD i mod 8 (amdkfd deals the bits round-robin; tools/ubench_cumask.hip
+// counts 30 / 2 CUs per XCD for 240 / 16 bits), inside an XCD the highest bits are the last CU of each shader engine.
+hipError_t CreateMaskedStream(int ingest_cus, int cus, hipStream_t* stream, bool ingest_side) {
+  if (ingest_cus <= 0) return hipStreamCreateWithFlags(stream, hipStreamNonBlocking);
+  const int split = cus - ingest_cus;
+  std::vector<uint32_t> mask(size_t(cus + 31) / 32, 0u);
+  for (int i = ingest_side ? split : 0; i < (ingest_side ? cus : split); ++i) mask[size_t(i) / 32] |= 1u << (i % 32);
+  return hipExtStreamCreateWithCUMask(stream, uint32_t(mask.size()), mask.data());
+}
+
+// Asynchronous ingest: frame copies run on streams of their own beside the tracking kernels.  The ledger decides
+// (m3t_ingest_plan.h), the methods carry its decisions out; DESIGN.md section 1 ("Frame ingest") states the protocol.
+struct Ingest {
+  static constexpr int kCopyStreams = m3t_ingest::kCopyStreams;
+  hipStream_t copy_stream[kCopyStreams] = {nullptr};
+  hipEvent_t copies_done[kCopyStreams] = {nullptr}, step_done[m3t_ingest::kStepEvents] = {nullptr};
+  m3t_ingest::Ledger ledger;
+  std::vector<void*> registered;  // Register
+  bool async() const { return ledger.async; }
+  bool untracked() const { return ledger.untracked; }
+  void LaunchedUntracked() { ledger.LaunchedUntracked(); }
+  hipStream_t Stream(int cs) const { return copy_stream[cs]; }
+  hipError_t Keep(const m3t_ingest::Ledger& before, hipError_t e) {  // a runtime call that fails leaves the ledger as it was
+    if (e != hipSuccess) ledger = before;
+    return e;
+  }
+  static hipError_t CreateStreams(int ingest_cus, int cus, hipStream_t (&streams)[kCopyStreams]) {
+    hipError_t e = CreateMaskedStream(ingest_cus, cus, &streams[0], true);
+    for (int i = 1; i < kCopyStreams && e == hipSuccess; ++i) e = hipStreamCreateWithFlags(&streams[i], hipStreamNonBlocking);
+    return e;
+  }
+  hipError_t EnsureStarted(int ingest_cus, int cus) {
+    const m3t_ingest::Ledger before = ledger;
+    if (!ledger.Start()) return hipSuccess;
+    hipError_t e = CreateStreams(ingest_cus, cus, copy_stream);
+    for (auto& ev : copies_done)
+      if (e == hipSuccess) e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+    for (auto& ev : step_done)
+      if (e == hipSuccess) e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+    return Keep(before, e);
+  }
+  // what a decision of the ledger asks for; cs: the copy stream that waits for a step event (-1: the host does)
+  hipError_t Obey(const m3t_ingest::Wait& w, int cs, hipStream_t compute) const {
+    if (w.kind == m3t_ingest::Wait::kComputeStream) return hipStreamSynchronize(compute);
+    if (w.kind == m3t_ingest::Wait::kNothing) return hipSuccess;
+    return cs < 0 ? hipEventSynchronize(step_done[w.event]) : hipStreamWaitEvent(copy_stream[cs], step_done[w.event], 0);
+  }
+  // a copy on copy stream cs overwrites a slot only behind the launches that read it last (step last_read) ...
+  hipError_t OrderCopy(int cs, long last_read, hipStream_t compute) {
+    const m3t_ingest::Ledger before = ledger;
+    return Keep(before, Obey(ledger.OrderCopy(cs, last_read), cs, compute));
+  }
+  // ... and the host waits for those launches
+  hipError_t WaitForReader(long last_read, hipStream_t compute) const { return Obey(ledger.WaitForReader(last_read), -1, compute); }
+  // the "slot copied" event of a camera or a slab (made on first use) behind what copy stream cs holds for the slot
+  hipError_t SlotCopied(std::vector<hipEvent_t>* events, int n_slots, int slot, int cs) {
+    if (events->size() < size_t(n_slots)) events->resize(size_t(n_slots), nullptr);
+    hipEvent_t& copied = (*events)[slot];
+    hipError_t e = copied ? hipSuccess : hipEventCreateWithFlags(&copied, hipEventDisableTiming);
+    if (e == hipSuccess && (e = hipEventRecord(copied, copy_stream[cs])) == hipSuccess) ledger.CopyEnqueued(cs);
+    return e;
+  }
+  // frames enqueued on the copy streams so far become visible to everything launched on `compute` from here on
+  hipError_t JoinPendingCopies(hipStream_t compute) {
+    const m3t_ingest::Ledger before = ledger;
+    hipError_t e = hipSuccess;
+    for (unsigned k = 0, pending = ledger.TakePending(); k < kCopyStreams && e == hipSuccess; ++k)
+      if ((pending >> k & 1u) && (e = hipEventRecord(copies_done[k], copy_stream[k])) == hipSuccess)
+        e = hipStreamWaitEvent(compute, copies_done[k], 0);
+    return Keep(before, e);
+  }
+  // Launches on `compute` read the current frames of the cameras listed (ids null: of all of them): a later asynchronous
+  // upload into one of these slots waits for exactly them, not for the ones enqueued after them
+  hipError_t MarkRead(hipStream_t compute, const std::vector<std::unique_ptr<Camera>>& cameras, const std::vector<int>* ids) {
+    const m3t_ingest::Ledger before = ledger;
+    const m3t_ingest::ReadMark mark = ledger.MarkRead();
+    if (mark.event < 0) return hipSuccess;
+    const hipError_t e = Keep(before, hipEventRecord(step_done[mark.event], compute));
+    for (size_t i = 0; e == hipSuccess && i < (ids ? ids->size() : cameras.size()); ++i) {
+      Camera& c = *cameras[ids ? size_t((*ids)[i]) : i];
+      c.last_read_step[c.current] = mark.step;
+    }
+    return e;
+  }
+  hipError_t SyncCopies() const {
+    hipError_t e = hipSuccess;
+    for (auto& cs : copy_stream)
+      if (cs && e == hipSuccess) e = hipStreamSynchronize(cs);
+    return e;
+  }
+  hipError_t Register(void* ptr, size_t bytes) {
+    const hipError_t e = hipHostRegister(ptr, bytes, hipHostRegisterDefault);
+    if (e == hipSuccess) registered.push_back(ptr);
+    return e;
+  }
+  bool IsRegistered(void* ptr) const { return std::find(registered.begin(), registered.end(), ptr) != registered.end(); }
+  hipError_t Unregister(void* ptr) {  // (behind every copy that may still read the buffer)
+    hipError_t e = SyncCopies();
+    if (e == hipSuccess && (e = hipHostUnregister(ptr)) == hipSuccess) registered.erase(std::find(registered.begin(), registered.end(), ptr));
+    return e;
+  }
+  void ReplaceStreams(const hipStream_t (&streams)[kCopyStreams]) {  // (synchronised by the caller: nothing is pending)
+    for (int i = 0; i < kCopyStreams; ++i) {
+      if (copy_stream[i]) (void)hipStreamDestroy(copy_stream[i]);
+      copy_stream[i] = streams[i];
+    }
+    (void)ledger.TakePending();
+  }
+  void Shutdown() {  // m3t_hip_destroy
+    for (auto& cs : copy_stream) {
+      if (!cs) continue;
+      (void)hipStreamSynchronize(cs);
+      (void)hipStreamDestroy(cs);
+    }
+    for (void* p : registered) (void)hipHostUnregister(p);
+    for (auto& e : copies_done)
+      if (e) (void)hipEventDestroy(e);
+    for (auto& e : step_done)
       if (e) (void)hipEventDestroy(e);
   }
 };
@@ -421,16 +553,7 @@ struct m3t_hip_context {
   int cam_stage_next = 0;
   MappedRing reset_args;  // m3t_hip_reset_bodies / _structures: the call's lists and poses, read in place by its launches
   std::vector<std::unique_ptr<Judge>> judges;  // m3t_hip_judge_create
-  // asynchronous ingest: frame copies run on their own stream beside the tracking kernels
-  static constexpr int kStepEvents = 16;
-  static constexpr int kCopyStreams = 4;  // cameras are spread round-robin: per-copy DMA latencies overlap
-  hipStream_t copy_stream[kCopyStreams] = {nullptr};
-  hipEvent_t copies_done[kCopyStreams] = {nullptr};
-  hipEvent_t step_done[kStepEvents] = {nullptr};
-  bool async_ingest = false, untracked_launches = false;
-  unsigned copies_pending = 0;  // bit s: copy stream s has frames not yet ordered before the compute stream
-  long step_counter = 0, copy_waited_step[kCopyStreams] = {-1, -1, -1, -1};
-  std::vector<void*> registered;
+  Ingest ingest;  // asynchronous frame uploads and their order against the launches that read the frames
   bool timing = false;        // m3t_hip_set_kernel_timing(1): an event pair around every launch
   bool timing_region = false; // m3t_hip_set_kernel_timing(2): ONE pair around all launches until the query
   hipEvent_t region_a = nullptr, region_b = nullptr;
@@ -644,10 +767,7 @@ int CreateCamera(Ctx* ctx, const m3t_intrinsics* intr, const float* w2c, bool de
   size_t row = size_t(intr->width) * (depth ? 2 : 3);
   c->pitch = uint32_t((row + 63) / 64 * 64);
   c->frame_bytes = size_t(c->pitch) * intr->height;
-  c->n_slots = 1;
-  c->has_image.assign(1, false);
-  c->last_read_step.assign(1, -1);
-  c->slot_is_roi.assign(1, false);
+  c->SetSlots(1);
   HIPCHK(c->ring.alloc(c->frame_bytes + 64));  // +64: pixels are fetched as one 4-byte load (B,G,R,+1)
   c->frames = c->ring.as<uint8_t>();
   c->slot_stride = c->frame_bytes;
@@ -1490,15 +1610,7 @@ void RoiMarkWholeFrames(Ctx* ctx, const int* ids, int n, int slot, hipStream_t s
 void RoiMarkWholeFrame(Ctx* ctx, int camera, int slot, hipStream_t stream) { RoiMarkWholeFrames(ctx, &camera, 1, slot, stream); }
 
 int UploadTables(Ctx* ctx) {
-  if (ctx->copies_pending) {
-    // frames enqueued on the copy stream so far become visible to everything launched from here on
-    for (int k = 0; k < Ctx::kCopyStreams; ++k) {
-      if (!(ctx->copies_pending >> k & 1u)) continue;
-      HIPCHK(hipEventRecord(ctx->copies_done[k], ctx->copy_stream[k]));
-      HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->copies_done[k], 0));
-    }
-    ctx->copies_pending = 0;
-  }
+  HIPCHK(ctx->ingest.JoinPendingCopies(ctx->stream));
   if (ctx->cams_dirty || ctx->tables_dirty || ctx->slots_dirty) {
     // Camera table versions: when every camera has the same number of ring slots, version s holds all cameras
     // looking at slot s, and a frame switch of the whole batch (m3t_hip_cameras_select_slot) only moves the
@@ -2014,8 +2126,10 @@ bool TreeStepSegmented(Ctx* ctx, const m3t_step::StepOverrides& overrides) {
   return true;
 }
 
-int Prepare(Ctx* ctx, bool need_images) {
-  if (ctx->async_ingest) ctx->untracked_launches = true;  // execute_tracking_step undoes this for itself
+// tracked: the caller's launches read no frames, or it marks them as readers itself (Ingest::MarkRead) -- the launches of
+// every other caller are behind no step event, and the next asynchronous upload waits for the whole compute stream
+int Prepare(Ctx* ctx, bool need_images, bool tracked = false) {
+  if (!tracked) ctx->ingest.LaunchedUntracked();
   if (need_images) {
     int r = CheckImages(ctx);
     if (r) return r;
@@ -2105,22 +2219,14 @@ int RequireWholeFrames(Ctx* ctx, const char* entry) {
 // (tables and poses that were waiting for their upload anyway)  changes_state: not a judgement without reset
 int BeginEnqueued(Ctx* ctx, bool changes_state) {
   HIPCHK(hipSetDevice(ctx->device));
-  const bool untracked_before = ctx->untracked_launches;
   if (changes_state && ctx->poses_dirty_host) ctx->roi_end_valid = false;  // poses set by the host: the last step's end no longer vouches for them
-  int r = Prepare(ctx, changes_state);
-  if (r) return r;
-  ctx->untracked_launches = untracked_before;  // reads poses only, or is tracked by the step_done event of EndEnqueued
-  return M3T_OK;
+  return Prepare(ctx, changes_state, true);  // reads poses only, or is marked as a reader by EndEnqueued
 }
 // cameras: whose current frames the call's launches read (null: none)
 int EndEnqueued(Ctx* ctx, MappedRing* ring, int slot, const std::vector<int>* cameras) {
   HIPCHK(hipGetLastError());
   HIPCHK(ring->Release(slot, ctx->stream));
-  if (cameras && ctx->async_ingest) {  // a later asynchronous upload into a slot these launches read waits for them
-    HIPCHK(hipEventRecord(ctx->step_done[ctx->step_counter % Ctx::kStepEvents], ctx->stream));
-    for (int c : *cameras) ctx->cameras[c]->last_read_step[ctx->cameras[c]->current] = ctx->step_counter;
-    ++ctx->step_counter;
-  }
+  if (cameras) HIPCHK(ctx->ingest.MarkRead(ctx->stream, ctx->cameras, cameras));
   return M3T_OK;
 }
 // the start-modality renderers of a call, from the two lists in its argument block
@@ -2146,24 +2252,32 @@ std::vector<float> PadVertices(const float* xyz, int n, size_t multiple) {
   return padded;
 }
 
-// The context's streams.  With CUs reserved for ingest (m3t_hip_reserve_ingest_cus) the compute stream runs on the
-// CUs of mask bits [0, CUs - n) and copy stream 0 -- the one the ROI pull kernel is launched on -- on bits
-// [CUs - n, CUs).  Bit i of a mask belongs to XCD i mod 8 (amdkfd deals the bits round-robin; tools/ubench_cumask.hip
-// counts 30 / 2 CUs per XCD for 240 / 16 bits), inside an XCD the highest bits are the last CU of each shader engine.
-hipError_t CreateMaskedStream(Ctx* ctx, hipStream_t* stream, bool ingest_side) {
-  if (ctx->ingest_cus <= 0) return hipStreamCreateWithFlags(stream, hipStreamNonBlocking);
-  const int cus = ctx->prop.multiProcessorCount, split = cus - ctx->ingest_cus;
-  std::vector<uint32_t> mask(size_t(cus + 31) / 32, 0u);
-  for (int i = ingest_side ? split : 0; i < (ingest_side ? cus : split); ++i) mask[size_t(i) / 32] |= 1u << (i % 32);
-  return hipExtStreamCreateWithCUMask(stream, uint32_t(mask.size()), mask.data());
+// The last step that read ring slot `slot` of any of these cameras (-1: none)
+long LastRead(Ctx* ctx, const int* ids, int n, int slot) {
+  long last_read = -1;
+  for (int i = 0; i < n; ++i) last_read = std::max(last_read, ctx->cameras[ids[i]]->last_read_step[slot]);
+  return last_read;
 }
-hipError_t CreateCopyStreams(Ctx* ctx) {
-  for (int i = 0; i < Ctx::kCopyStreams; ++i) {
-    const hipError_t e = i == 0 ? CreateMaskedStream(ctx, &ctx->copy_stream[i], true)
-                                : hipStreamCreateWithFlags(&ctx->copy_stream[i], hipStreamNonBlocking);
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
+// Whole frames into ring slot `slot` on copy stream cs -- of one camera, or of n cameras that lie one behind the other
+// in a slab and in the host block (rows of row_step bytes): order, transfer, mark ("Frame
+// ingest").  copied: the slot-copied events of the camera or the slab.  The arguments have been validated.
+int UploadWholeFrames(Ctx* ctx, const int* ids, int n, int slot, const void* src, size_t row_step, int cs,
+                      std::vector<hipEvent_t>* copied) {
+  const Camera& c0 = *ctx->cameras[ids[0]];
+  const size_t row = size_t(c0.intr.width) * (c0.is_depth ? 2 : 3);
+  HIPCHK(hipSetDevice(ctx->device));
+  HIPCHK(ctx->ingest.EnsureStarted(ctx->ingest_cus, ctx->prop.multiProcessorCount));
+  HIPCHK(ctx->ingest.OrderCopy(cs, LastRead(ctx, ids, n, slot), ctx->stream));
+  hipStream_t stream = ctx->ingest.Stream(cs);
+  if (row_step == c0.pitch)  // contiguous on both sides: one linear DMA transfer
+    HIPCHK(hipMemcpyAsync(c0.frame(slot), src, c0.frame_bytes * size_t(n) - (c0.pitch - row), hipMemcpyHostToDevice, stream));
+  else
+    HIPCHK(hipMemcpy2DAsync(c0.frame(slot), c0.pitch, src, row_step, row, size_t(c0.intr.height) * size_t(n),
+                            hipMemcpyHostToDevice, stream));
+  for (int i = 0; i < n; ++i) ctx->cameras[ids[i]]->has_image[slot] = true;
+  RoiMarkWholeFrames(ctx, ids, n, slot, stream);
+  HIPCHK(ctx->ingest.SlotCopied(copied, c0.n_slots, slot, cs));
+  return M3T_OK;
 }
 
 }  // namespace
@@ -2189,7 +2303,7 @@ int m3t_hip_create(m3t_hip_context** out, int device_id) {
   auto ctx = std::make_unique<m3t_hip_context>();
   ctx->device = device_id;
   if ((e = hipSetDevice(device_id)) != hipSuccess || (e = hipGetDeviceProperties(&ctx->prop, device_id)) != hipSuccess ||
-      (e = CreateMaskedStream(ctx.get(), &ctx->stream, false)) != hipSuccess) {
+      (e = CreateMaskedStream(0, ctx->prop.multiProcessorCount, &ctx->stream, false)) != hipSuccess) {
     g_create_error = std::string("device initialisation failed: ") + hipGetErrorString(e);
     return M3T_ERR_DEVICE;
   }
@@ -2205,16 +2319,7 @@ void m3t_hip_destroy(m3t_hip_context* ctx) {
     (void)hipStreamSynchronize(ctx->stream);
     (void)hipStreamDestroy(ctx->stream);
   }
-  for (auto& cs : ctx->copy_stream) {
-    if (!cs) continue;
-    (void)hipStreamSynchronize(cs);
-    (void)hipStreamDestroy(cs);
-  }
-  for (void* p : ctx->registered) (void)hipHostUnregister(p);
-  for (auto& e : ctx->copies_done)
-    if (e) (void)hipEventDestroy(e);
-  for (auto& e : ctx->step_done)
-    if (e) (void)hipEventDestroy(e);
+  ctx->ingest.Shutdown();
   for (int i = 0; i < m3t_hip_context::kStage; ++i) {
     if (ctx->cam_stage[i]) (void)hipHostFree(ctx->cam_stage[i]);
     if (ctx->cam_stage_done[i]) (void)hipEventDestroy(ctx->cam_stage_done[i]);
@@ -2365,11 +2470,7 @@ int m3t_hip_camera_set_ring(m3t_hip_context* ctx, int id, int n_slots) {
   c.frames = c.ring.as<uint8_t>();
   c.slot_stride = c.frame_bytes;
   c.slab = -1;
-  c.n_slots = n_slots;
-  c.current = 0;
-  c.has_image.assign(n_slots, false);
-  c.last_read_step.assign(n_slots, -1);
-  c.slot_is_roi.assign(n_slots, false);
+  c.SetSlots(n_slots);
   if (ctx->roi_enabled) ctx->tables_dirty = true;  // (the rectangle table has a row per ring slot)
   ctx->cams_dirty = true;
   return M3T_OK;
@@ -2383,19 +2484,14 @@ int m3t_hip_host_register(m3t_hip_context* ctx, void* ptr, size_t bytes) {
   CHECK_CTX();
   REQUIRE(ptr && bytes, M3T_ERR_INVALID_ARGUMENT, "null buffer");
   HIPCHK(hipSetDevice(ctx->device));
-  HIPCHK(hipHostRegister(ptr, bytes, hipHostRegisterDefault));
-  ctx->registered.push_back(ptr);
+  HIPCHK(ctx->ingest.Register(ptr, bytes));
   return M3T_OK;
 }
 int m3t_hip_host_unregister(m3t_hip_context* ctx, void* ptr) {
   CHECK_CTX();
-  auto it = std::find(ctx->registered.begin(), ctx->registered.end(), ptr);
-  REQUIRE(it != ctx->registered.end(), M3T_ERR_INVALID_ARGUMENT, "buffer was not registered with this context");
+  REQUIRE(ctx->ingest.IsRegistered(ptr), M3T_ERR_INVALID_ARGUMENT, "buffer was not registered with this context");
   HIPCHK(hipSetDevice(ctx->device));
-  for (auto& cs : ctx->copy_stream)
-    if (cs) HIPCHK(hipStreamSynchronize(cs));
-  HIPCHK(hipHostUnregister(ptr));
-  ctx->registered.erase(it);
+  HIPCHK(ctx->ingest.Unregister(ptr));
   return M3T_OK;
 }
 int m3t_hip_camera_upload_slot_async(m3t_hip_context* ctx, int id, int slot, const void* pixels, size_t row_step) {
@@ -2403,40 +2499,8 @@ int m3t_hip_camera_upload_slot_async(m3t_hip_context* ctx, int id, int slot, con
   REQUIRE(id >= 0 && id < int(ctx->cameras.size()) && pixels, M3T_ERR_INVALID_ARGUMENT, "bad camera id");
   Camera& c = *ctx->cameras[id];
   REQUIRE(slot >= 0 && slot < c.n_slots, M3T_ERR_INVALID_ARGUMENT, "bad frame slot");
-  size_t row = size_t(c.intr.width) * (c.is_depth ? 2 : 3);
-  REQUIRE(row_step >= row, M3T_ERR_INVALID_ARGUMENT, "row_step smaller than one image row");
-  HIPCHK(hipSetDevice(ctx->device));
-  if (!ctx->async_ingest) {
-    HIPCHK(CreateCopyStreams(ctx));
-    for (auto& e : ctx->copies_done) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    for (auto& e : ctx->step_done) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    ctx->async_ingest = true;
-    ctx->untracked_launches = true;  // whatever ran before was not tracked by step events
-  }
-  const int cs = id % Ctx::kCopyStreams;
-  if (ctx->untracked_launches) {
-    // sub-step launches (or anything before the first asynchronous upload) carry no step event
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    ctx->untracked_launches = false;
-  } else if (c.last_read_step[slot] > ctx->copy_waited_step[cs]) {
-    // overwrite only after the last step that read this slot (a recycled event is a later step: still
-    // safe); a copy stream is in order, so one wait per step covers all of its cameras
-    HIPCHK(hipStreamWaitEvent(ctx->copy_stream[cs], ctx->step_done[c.last_read_step[slot] % Ctx::kStepEvents], 0));
-    ctx->copy_waited_step[cs] = c.last_read_step[slot];
-  }
-  uint8_t* dst = c.frame(slot);
-  if (row_step == c.pitch)  // contiguous on both sides: one linear DMA transfer
-    HIPCHK(hipMemcpyAsync(dst, pixels, c.frame_bytes - (c.pitch - row), hipMemcpyHostToDevice, ctx->copy_stream[cs]));
-  else
-    HIPCHK(hipMemcpy2DAsync(dst, c.pitch, pixels, row_step, row, c.intr.height, hipMemcpyHostToDevice,
-                            ctx->copy_stream[cs]));
-  c.has_image[slot] = true;
-  RoiMarkWholeFrame(ctx, id, slot, ctx->copy_stream[cs]);
-  if (c.slot_copied.size() < size_t(c.n_slots)) c.slot_copied.resize(size_t(c.n_slots), nullptr);
-  if (!c.slot_copied[slot]) HIPCHK(hipEventCreateWithFlags(&c.slot_copied[slot], hipEventDisableTiming));
-  HIPCHK(hipEventRecord(c.slot_copied[slot], ctx->copy_stream[cs]));
-  ctx->copies_pending |= 1u << cs;
-  return M3T_OK;
+  REQUIRE(row_step >= size_t(c.intr.width) * (c.is_depth ? 2 : 3), M3T_ERR_INVALID_ARGUMENT, "row_step smaller than one image row");
+  return UploadWholeFrames(ctx, &id, 1, slot, pixels, row_step, id % Ingest::kCopyStreams, &c.slot_copied);
 }
 // Wait until the last upload into (camera, slot) -- camera_upload_slot_async, a batch upload, a rectangle pull -- has
 // left its host buffer, and for nothing else: the copies of other cameras and of this camera's other slots stay in
@@ -2448,25 +2512,20 @@ int m3t_hip_camera_slot_sync(m3t_hip_context* ctx, int id, int slot) {
   Camera& c = *ctx->cameras[id];
   REQUIRE(slot >= 0 && slot < c.n_slots, M3T_ERR_INVALID_ARGUMENT, "bad frame slot");
   HIPCHK(hipSetDevice(ctx->device));
+  hipEvent_t slab_copied = nullptr;  // behind the last batch upload / rectangle pull into the slot
+  if (c.slab >= 0 && size_t(slot) < ctx->slabs[size_t(c.slab)]->slot_copied.size())
+    slab_copied = ctx->slabs[size_t(c.slab)]->slot_copied[slot];
   if (c.slot_is_roi[slot]) {
     // a rectangle went into the slot (m3t_hip_cameras_upload_batch_roi_async): the host block is read by the pull and,
     // should a body outrun its rectangle, again by the repair of the step that reads the slot -- both must be over
-    hipEvent_t pulled = nullptr;
-    if (c.slab >= 0 && size_t(slot) < ctx->slabs[size_t(c.slab)]->slot_copied.size())
-      pulled = ctx->slabs[size_t(c.slab)]->slot_copied[slot];
-    if (pulled) HIPCHK(hipEventSynchronize(pulled));
-    else if (ctx->async_ingest && ctx->copy_stream[0]) HIPCHK(hipStreamSynchronize(ctx->copy_stream[0]));
-    if (c.last_read_step[slot] >= 0 && c.last_read_step[slot] + Ctx::kStepEvents > ctx->step_counter)
-      HIPCHK(hipEventSynchronize(ctx->step_done[c.last_read_step[slot] % Ctx::kStepEvents]));
-    else if (c.last_read_step[slot] >= 0)
-      HIPCHK(hipStreamSynchronize(ctx->stream));
+    if (slab_copied) HIPCHK(hipEventSynchronize(slab_copied));
+    else if (ctx->ingest.Stream(0)) HIPCHK(hipStreamSynchronize(ctx->ingest.Stream(0)));
+    HIPCHK(ctx->ingest.WaitForReader(c.last_read_step[slot], ctx->stream));
     return M3T_OK;
   }
   // (a camera may have been fed both ways: its own uploads and batch uploads of its slab; an event that has long
   // completed costs nothing to wait for)
-  if (c.slab >= 0 && size_t(slot) < ctx->slabs[size_t(c.slab)]->slot_copied.size() &&
-      ctx->slabs[size_t(c.slab)]->slot_copied[slot])
-    HIPCHK(hipEventSynchronize(ctx->slabs[size_t(c.slab)]->slot_copied[slot]));
+  if (slab_copied) HIPCHK(hipEventSynchronize(slab_copied));
   if (size_t(slot) >= c.slot_copied.size() || !c.slot_copied[slot]) return M3T_OK;  // nothing (else) was enqueued
   HIPCHK(hipEventSynchronize(c.slot_copied[slot]));
   return M3T_OK;
@@ -2501,11 +2560,7 @@ int m3t_hip_cameras_set_ring(m3t_hip_context* ctx, const int* ids, int n, int n_
     c.slab_index = i;
     c.frames = slab->mem.as<uint8_t>() + size_t(i) * frame_bytes;
     c.slot_stride = frame_bytes * size_t(n);
-    c.n_slots = n_slots;
-    c.current = 0;
-    c.has_image.assign(n_slots, false);
-    c.last_read_step.assign(n_slots, -1);
-    c.slot_is_roi.assign(n_slots, false);
+    c.SetSlots(n_slots);
     if (ctx->roi_enabled) ctx->tables_dirty = true;  // (the rectangle table has a row per ring slot)
   }
   ctx->slabs.push_back(std::move(slab));
@@ -2529,8 +2584,7 @@ int m3t_hip_cameras_upload_batch_async(m3t_hip_context* ctx, const int* ids, int
     if (c.slab < 0 || c.slab != c0.slab || c.slab_index != c0.slab_index + i) one_block = false;
   }
   const Camera& c0 = *ctx->cameras[ids[0]];
-  const size_t row = size_t(c0.intr.width) * (c0.is_depth ? 2 : 3);
-  REQUIRE(row_step >= row, M3T_ERR_INVALID_ARGUMENT, "row_step smaller than one image row");
+  REQUIRE(row_step >= size_t(c0.intr.width) * (c0.is_depth ? 2 : 3), M3T_ERR_INVALID_ARGUMENT, "row_step smaller than one image row");
   if (!(one_block && camera_stride == size_t(c0.intr.height) * row_step)) {
     for (int i = 0; i < n; ++i) {  // scattered on one side: one transfer per camera, still without a host round trip each
       int r = m3t_hip_camera_upload_slot_async(ctx, ids[i], slot, static_cast<const uint8_t*>(base) + size_t(i) * camera_stride,
@@ -2539,43 +2593,8 @@ int m3t_hip_cameras_upload_batch_async(m3t_hip_context* ctx, const int* ids, int
     }
     return M3T_OK;
   }
-  HIPCHK(hipSetDevice(ctx->device));
-  if (!ctx->async_ingest) {
-    HIPCHK(CreateCopyStreams(ctx));
-    for (auto& e : ctx->copies_done) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    for (auto& e : ctx->step_done) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    ctx->async_ingest = true;
-    ctx->untracked_launches = true;
-  }
-  const int cs = 0;
-  long last_read = -1;
-  for (int i = 0; i < n; ++i) last_read = std::max(last_read, ctx->cameras[ids[i]]->last_read_step[slot]);
-  if (ctx->untracked_launches) {
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    ctx->untracked_launches = false;
-  } else if (last_read > ctx->copy_waited_step[cs]) {  // overwrite only after the last step that read this slot
-    HIPCHK(hipStreamWaitEvent(ctx->copy_stream[cs], ctx->step_done[last_read % Ctx::kStepEvents], 0));
-    ctx->copy_waited_step[cs] = last_read;
-  }
-  uint8_t* dst = c0.frame(slot);
-  if (row_step == c0.pitch)
-    HIPCHK(hipMemcpyAsync(dst, base, c0.frame_bytes * size_t(n) - (c0.pitch - row), hipMemcpyHostToDevice,
-                          ctx->copy_stream[cs]));
-  else
-    HIPCHK(hipMemcpy2DAsync(dst, c0.pitch, base, row_step, row, size_t(c0.intr.height) * size_t(n), hipMemcpyHostToDevice,
-                            ctx->copy_stream[cs]));
-  for (int i = 0; i < n; ++i) ctx->cameras[ids[i]]->has_image[slot] = true;
-  RoiMarkWholeFrames(ctx, ids, n, slot, ctx->copy_stream[cs]);
-  // m3t_hip_camera_slot_sync: every camera of the batch waits for this transfer before its host block is written again
   // (also reached from cameras_upload_batch_roi_async whenever rectangles are not possible)
-  {
-    FrameSlab& slab = *ctx->slabs[size_t(c0.slab)];
-    if (slab.slot_copied.size() < size_t(c0.n_slots)) slab.slot_copied.resize(size_t(c0.n_slots), nullptr);
-    if (!slab.slot_copied[slot]) HIPCHK(hipEventCreateWithFlags(&slab.slot_copied[slot], hipEventDisableTiming));
-    HIPCHK(hipEventRecord(slab.slot_copied[slot], ctx->copy_stream[cs]));
-  }
-  ctx->copies_pending |= 1u << cs;
-  return M3T_OK;
+  return UploadWholeFrames(ctx, ids, n, slot, base, row_step, 0, &ctx->slabs[size_t(c0.slab)]->slot_copied);
 }
 // ROI ingest (m3t_ingest.hip).  enable: the fused rigid launches record the poses their searches run at,
 // and m3t_hip_cameras_upload_batch_roi_async may upload rectangles instead of frames; margin_px: how far (in pixels,
@@ -2617,38 +2636,26 @@ int m3t_hip_reserve_ingest_cus(m3t_hip_context* ctx, int n_cus) {
   if (n_cus == ctx->ingest_cus) return M3T_OK;
   HIPCHK(hipSetDevice(ctx->device));
   HIPCHK(hipStreamSynchronize(ctx->stream));
-  for (auto& cs : ctx->copy_stream)
-    if (cs) HIPCHK(hipStreamSynchronize(cs));
+  HIPCHK(ctx->ingest.SyncCopies());
   // all new streams first, then the swap: a failure leaves the context as it was.  (hipExtStreamCreateWithCUMask makes
   // BLOCKING streams: while CUs are reserved, work on the legacy NULL stream -- a plain hipMemcpy, torch's default
   // stream -- synchronises with the compute stream and copy stream 0; keep such work off the device meanwhile, or
   // the pull / step overlap is lost.)
-  const int before = ctx->ingest_cus;
-  ctx->ingest_cus = n_cus;
-  hipStream_t compute = nullptr;
-  hipStream_t copies_old[Ctx::kCopyStreams];
-  for (int i = 0; i < Ctx::kCopyStreams; ++i) {
-    copies_old[i] = ctx->copy_stream[i];
-    ctx->copy_stream[i] = nullptr;
-  }
-  hipError_t e = CreateMaskedStream(ctx, &compute, false);
-  if (e == hipSuccess && ctx->async_ingest) e = CreateCopyStreams(ctx);
+  hipStream_t compute = nullptr, copies[Ingest::kCopyStreams] = {nullptr};
+  hipError_t e = CreateMaskedStream(n_cus, ctx->prop.multiProcessorCount, &compute, false);
+  if (e == hipSuccess && ctx->ingest.async()) e = Ingest::CreateStreams(n_cus, ctx->prop.multiProcessorCount, copies);
   if (e != hipSuccess) {
     (void)hipGetLastError();
     if (compute) (void)hipStreamDestroy(compute);
-    for (int i = 0; i < Ctx::kCopyStreams; ++i) {
-      if (ctx->copy_stream[i]) (void)hipStreamDestroy(ctx->copy_stream[i]);
-      ctx->copy_stream[i] = copies_old[i];
-    }
-    ctx->ingest_cus = before;
+    for (hipStream_t made : copies)
+      if (made) (void)hipStreamDestroy(made);
     return Fail(ctx, M3T_ERR_UNSUPPORTED, "this device / runtime does not create CU-masked streams");
   }
   (void)hipStreamDestroy(ctx->stream);
   ctx->stream = compute;
-  for (auto& cs : copies_old)
-    if (cs) (void)hipStreamDestroy(cs);
+  ctx->ingest.ReplaceStreams(copies);
+  ctx->ingest_cus = n_cus;
   ctx->compute_cus = ctx->prop.multiProcessorCount - n_cus;
-  ctx->copies_pending = 0;
   return M3T_OK;
 }
 // m3t_hip_cameras_upload_batch_async for the trackers' rectangles only: ONE kernel on the copy stream computes every
@@ -2661,7 +2668,7 @@ int m3t_hip_cameras_upload_batch_roi_async(m3t_hip_context* ctx, const int* ids,
   CHECK_CTX();
   REQUIRE(ids && n >= 1 && base, M3T_ERR_INVALID_ARGUMENT, "bad arguments");
   bool pull = ctx->roi_enabled && ctx->roi_recorded && ctx->roi_snapshot_valid && ctx->n_roi_items > 0 &&
-              !ctx->tables_dirty && !ctx->cams_dirty && ctx->async_ingest;
+              !ctx->tables_dirty && !ctx->cams_dirty && ctx->ingest.async();
   for (int i = 0; i < n && pull; ++i) {
     if (ids[i] < 0 || ids[i] >= int(ctx->cameras.size())) { pull = false; break; }
     const Camera& c = *ctx->cameras[ids[i]];
@@ -2688,6 +2695,7 @@ int m3t_hip_cameras_upload_batch_roi_async(m3t_hip_context* ctx, const int* ids,
   if (!pull) return m3t_hip_cameras_upload_batch_async(ctx, ids, n, slot, base, camera_stride, row_step);
   HIPCHK(hipSetDevice(ctx->device));
   const int cs = 0;
+  hipStream_t copy_stream = ctx->ingest.Stream(cs);
   bool consecutive = true;
   for (int i = 0; i < n; ++i) consecutive = consecutive && ids[i] == ids[0] + i;
   const int* d_ids = ctx->d_roi_all_cam_ids.as<int>() + ids[0];
@@ -2701,7 +2709,7 @@ int m3t_hip_cameras_upload_batch_roi_async(m3t_hip_context* ctx, const int* ids,
       if (l.first == wanted) list = l.second.get();
     if (!list) {
       if (ctx->roi_cam_id_lists.size() >= Ctx::kRoiScatteredLists) {  // (rare: camera lists that keep changing)
-        HIPCHK(hipStreamSynchronize(ctx->copy_stream[cs]));
+        HIPCHK(hipStreamSynchronize(copy_stream));
         HIPCHK(hipStreamSynchronize(ctx->stream));  // (a repair may still read an old list)
         for (auto& sources : ctx->roi_sources) sources.clear();
         ctx->roi_cam_id_lists.clear();
@@ -2714,31 +2722,23 @@ int m3t_hip_cameras_upload_batch_roi_async(m3t_hip_context* ctx, const int* ids,
     }
     d_ids = list->as<int>();
   }
-  long last_read = -1;
-  for (int i = 0; i < n; ++i) last_read = std::max(last_read, ctx->cameras[ids[i]]->last_read_step[slot]);
-  if (ctx->untracked_launches) {
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    ctx->untracked_launches = false;
-  } else if (last_read > ctx->copy_waited_step[cs]) {  // overwrite only after the last step that read this slot
-    HIPCHK(hipStreamWaitEvent(ctx->copy_stream[cs], ctx->step_done[last_read % Ctx::kStepEvents], 0));
-    ctx->copy_waited_step[cs] = last_read;
-  }
-  HIPCHK(hipStreamWaitEvent(ctx->copy_stream[cs], ctx->roi_snapshot_done[ctx->roi_use], 0));  // the poses the rectangles come from
+  HIPCHK(ctx->ingest.OrderCopy(cs, LastRead(ctx, ids, n, slot), ctx->stream));
+  HIPCHK(hipStreamWaitEvent(copy_stream, ctx->roi_snapshot_done[ctx->roi_use], 0));  // the poses the rectangles come from
   const bool adaptive = ctx->roi_adaptive && ctx->roi_prev >= 0;
-  if (adaptive) HIPCHK(hipStreamWaitEvent(ctx->copy_stream[cs], ctx->roi_snapshot_done[ctx->roi_prev], 0));
+  if (adaptive) HIPCHK(hipStreamWaitEvent(copy_stream, ctx->roi_snapshot_done[ctx->roi_prev], 0));
   const Camera& c0 = *ctx->cameras[ids[0]];
   // the camera table is only read for intrinsics and world2camera here: any slot version will do (the first one)
   m3t_roi_rect* rects = ctx->d_roi_rects.as<m3t_roi_rect>() + size_t(slot) * ctx->cameras.size();
   const size_t snapshot_floats = ctx->d_roi_pose_snapshot.bytes / (4 * Ctx::kRoiSnapshots);
   const float* snapshots = ctx->d_roi_pose_snapshot.as<float>();
   // (without a second snapshot an adaptive upload takes the whole margin)
-  hipLaunchKernelGGL(roi_rect_kernel, dim3((n + 63) / 64), dim3(64), 0, ctx->copy_stream[cs],
+  hipLaunchKernelGGL(roi_rect_kernel, dim3((n + 63) / 64), dim3(64), 0, copy_stream,
                      ctx->d_roi_items.as<RoiItemDev>(), ctx->d_roi_item_first.as<int>(), d_ids, n,
                      ctx->d_cams.as<CameraDev>(), snapshots + size_t(ctx->roi_use) * snapshot_floats,
                      adaptive ? snapshots + size_t(ctx->roi_prev) * snapshot_floats : (const float*)nullptr,
                      adaptive ? ctx->d_roi_motion_peak.as<float>() : (float*)nullptr, ctx->roi_margin_px,
                      std::min(ctx->roi_margin_px, 4.0f), rects);
-  hipLaunchKernelGGL(roi_pull_kernel, dim3((c0.intr.height + 7) / 8, n), dim3(256), 0, ctx->copy_stream[cs],
+  hipLaunchKernelGGL(roi_pull_kernel, dim3((c0.intr.height + 7) / 8, n), dim3(256), 0, copy_stream,
                      d_ids, rects, src, camera_stride, uint32_t(row_step), c0.frame(slot),
                      c0.frame_bytes, c0.pitch, c0.is_depth ? 2 : 3);
   HIPCHK(hipGetLastError());
@@ -2748,12 +2748,8 @@ int m3t_hip_cameras_upload_batch_roi_async(m3t_hip_context* ctx, const int* ids,
     c.has_image[slot] = true;
     c.slot_is_roi[slot] = true;
   }
-  {  // m3t_hip_camera_slot_sync waits for THIS pull, not for whatever else the copy stream carries by then
-    FrameSlab& slab = *ctx->slabs[size_t(c0.slab)];
-    if (slab.slot_copied.size() < size_t(c0.n_slots)) slab.slot_copied.resize(size_t(c0.n_slots), nullptr);
-    if (!slab.slot_copied[slot]) HIPCHK(hipEventCreateWithFlags(&slab.slot_copied[slot], hipEventDisableTiming));
-    HIPCHK(hipEventRecord(slab.slot_copied[slot], ctx->copy_stream[cs]));
-  }
+  // m3t_hip_camera_slot_sync waits for THIS pull, not for whatever else the copy stream carries by then
+  HIPCHK(ctx->ingest.SlotCopied(&ctx->slabs[size_t(c0.slab)]->slot_copied, c0.n_slots, slot, cs));
   {  // where the whole frames are, should a body outrun its rectangle (the repair of the step that reads this slot)
     auto& sources = ctx->roi_sources[size_t(slot)];
     for (size_t k = 0; k < sources.size();) {
@@ -2770,7 +2766,6 @@ int m3t_hip_cameras_upload_batch_roi_async(m3t_hip_context* ctx, const int* ids,
     source.row_step = uint32_t(row_step);
     sources.push_back(std::move(source));
   }
-  ctx->copies_pending |= 1u << cs;
   return M3T_OK;
 }
 // Bodies whose steps since the last call needed pixels outside the rectangle that had been uploaded: up to `capacity`
@@ -2812,8 +2807,7 @@ int m3t_hip_roi_get_unrecovered(m3t_hip_context* ctx, int* bodies, int capacity,
 int m3t_hip_ingest_sync(m3t_hip_context* ctx) {
   CHECK_CTX();
   HIPCHK(hipSetDevice(ctx->device));
-  for (auto& cs : ctx->copy_stream)
-    if (cs) HIPCHK(hipStreamSynchronize(cs));
+  HIPCHK(ctx->ingest.SyncCopies());
   return M3T_OK;
 }
 int m3t_hip_camera_select_slot(m3t_hip_context* ctx, int id, int slot) {
@@ -3630,7 +3624,7 @@ int m3t_hip_texture_modality_set_features(m3t_hip_context* ctx, int modality, co
     HIPCHK(hipMemcpyAsync(target + (TF_HEADER_WORDS + 2 * M3T_TEXTURE_MAX_FEATURES) * 4, block + head_bytes, descriptor_bytes,
                           hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(m->uploads.Release(slot, ctx->stream));
-  if (ctx->async_ingest) ctx->untracked_launches = true;
+  ctx->ingest.LaunchedUntracked();  // (copies on the compute stream behind no step event)
   return M3T_OK;
 }
 int m3t_hip_texture_modality_get_points(m3t_hip_context* ctx, int modality, m3t_texture_data_point* out, int capacity,
@@ -5369,11 +5363,9 @@ int m3t_hip_execute_tracking_step(m3t_hip_context* ctx, int iteration) {
   CHECK_CTX();
   HIPCHK(hipSetDevice(ctx->device));
   const StepOverrides overrides = m3t_step::ReadStepOverrides();  // every step: tests change them between two steps
-  const bool untracked_before = ctx->untracked_launches;
   const bool host_poses_before = ctx->poses_dirty_host;  // (Prepare uploads them)
-  int r = Prepare(ctx, true);
+  int r = Prepare(ctx, true, true);  // a whole step is marked as a reader below
   if (r) return r;
-  ctx->untracked_launches = untracked_before;  // a whole step is tracked by its step_done event below
   if ((r = CheckSplitExchange(ctx))) return r;  // an earlier step that was abandoned on the device
   const bool rigid_fused = ctx->fused_mode >= 1 && ctx->fused_possible && !ctx->Distributed();
   bool roi_frames = false;  // does this step read a slot that holds a rectangle only
@@ -5389,7 +5381,7 @@ int m3t_hip_execute_tracking_step(m3t_hip_context* ctx, int iteration) {
     // before this step had to wait for its own frame, so the next pull can follow the current one at once -- unless
     // something else touched the poses in between.  The snapshot before that one (adaptive margins) is the start of
     // the previous step.
-    if (ctx->roi_end_valid && !host_poses_before && !untracked_before) {
+    if (ctx->roi_end_valid && !host_poses_before && !ctx->ingest.untracked()) {
       ctx->roi_prev = ctx->roi_use;
       ctx->roi_use = ctx->roi_end_index;
     } else {
@@ -5436,13 +5428,7 @@ int m3t_hip_execute_tracking_step(m3t_hip_context* ctx, int iteration) {
     HIPCHK(hipEventRecord(ctx->roi_snapshot_done[ctx->roi_end_index], ctx->stream));
     ctx->roi_end_valid = true;
   }
-  if (ctx->async_ingest) {
-    // remember which frame slots this step reads, so that a later asynchronous upload into one of
-    // them waits for exactly this step and not for the ones enqueued after it
-    HIPCHK(hipEventRecord(ctx->step_done[ctx->step_counter % Ctx::kStepEvents], ctx->stream));
-    for (auto& cam : ctx->cameras) cam->last_read_step[cam->current] = ctx->step_counter;
-    ++ctx->step_counter;
-  }
+  HIPCHK(ctx->ingest.MarkRead(ctx->stream, ctx->cameras, nullptr));  // the current slot of every camera
   return M3T_OK;
 }
 // Refiner::RefinePoses src/refiner.cpp:76-117 (one launch per sub-step)

@@ -264,6 +264,87 @@ def test_async_ingest_matches_blocking_upload():
     assert np.array_equal(poses[0][-1], poses[1][-1])
 
 
+@pytest.fixture(scope="module")
+def long_ingest_reference():
+    """20 frames of two objects and their last poses under the blocking hand-over (computed once for both loops)"""
+    inputs = scenes.Inputs(2, 20, n_divides=2)
+    inst = scenes.Instance(util.open_hip(), inputs)
+    inst.upload_frame(0)
+    assert inst.tracker.StartModalities(0)
+    for k in range(1, inputs.n_frames):
+        inst.upload_frame(k)
+        assert inst.tracker.ExecuteTrackingStep(k)
+    return inputs, np.stack(inst.poses())
+
+
+@pytest.mark.parametrize("loop", ["two slots", "a slot unread for 17 steps"])
+def test_async_ingest_past_the_step_event_ring(loop, long_ingest_reference):
+    """More steps than the library keeps step events (16), so that an upload and a slot sync meet an event index that a
+    later step has taken again; the last poses equal those of the blocking hand-over bit for bit.  Frames are counted
+    from 0 and the step on frame k is ExecuteTrackingStep(k); the library numbers the steps behind the first
+    asynchronous upload from 0, so the step on frame k has id k - 1 and records step event (k - 1) % 16.
+    "two slots": the loop of test_async_ingest_matches_blocking_upload over all 20 frames (per-camera rings and uploads).
+    "a slot unread for 17 steps": one shared ring of three slots with ROI ingest on.  Frame 1 goes into slot 2 through
+    cameras_upload_batch_roi_async (as whole frames: no step recorded yet) and only its step (id 0, event 0) reads the
+    slot; slots 0 and 1 alternate for frames 2-18, filled by the blocking camera_upload_slot, so the copy stream waits
+    for none of their steps; frame 19 goes into slot 2 behind the step on frame 18 (id 17) through
+    cameras_upload_batch_roi_async (as rectangles) and its step reads it.  By then event 0 belongs to the step with id
+    16: the upload waits for that recycled event, and camera_slot_sync on the slot (0 + 16 is not beyond the 18 steps
+    so far) answers with the whole compute stream."""
+    inputs, want = long_ingest_reference
+    n, n_frames = inputs.n_objects, inputs.n_frames
+    hip = util.open_hip()
+    inst = scenes.Instance(hip, inputs)
+    if loop != "two slots":
+        hip.call("set_roi_ingest", 1, C.c_float(24.0))
+    inst.upload_frame(0)
+    assert inst.tracker.StartModalities(0)
+    blocks = [np.stack([inputs.color[i][k] for i in range(n)]) for k in range(n_frames)]
+    for b in blocks:
+        inst.tracker.register_host_buffer(b)
+    if loop == "two slots":
+        for cam in inst.color_cams:
+            cam.set_ring(2)
+
+        def slot_of(k):
+            return k % 2
+
+        def upload(k):
+            for i, cam in enumerate(inst.color_cams):
+                cam.upload_slot(slot_of(k), blocks[k][i], asynchronous=True)
+    else:
+        ids = (C.c_int * n)(*[cam.id for cam in inst.color_cams])
+        hip.call("cameras_set_ring", ids, n, 3)
+
+        def slot_of(k):
+            return 2 if k in (1, n_frames - 1) else k % 2
+
+        def upload(k):
+            b = blocks[k]
+            if slot_of(k) == 2:
+                hip.call("cameras_upload_batch_roi_async", ids, n, 2, b.ctypes.data_as(C.c_void_p), b.strides[0], b.strides[1])
+            else:
+                for i, cam in enumerate(inst.color_cams):
+                    cam.upload_slot(slot_of(k), b[i])
+    upload(1)
+    for k in range(1, n_frames):
+        inst.tracker.select_slot(slot_of(k))
+        assert inst.tracker.ExecuteTrackingStep(k)
+        if k + 1 < n_frames:
+            upload(k + 1)
+            if loop != "two slots" and k + 1 == n_frames - 1:
+                inst.color_cams[0].slot_sync(2)
+    inst.tracker.ingest_sync()
+    got = np.stack(inst.poses())
+    if loop != "two slots":
+        kernel = C.create_string_buffer(128)
+        hip.call("get_step_kernel", kernel, 128)
+        assert b"_guard_kernel" in kernel.value, kernel.value  # the last step read rectangles: slot 2 was synced as a rectangle slot
+    for b in blocks:
+        inst.tracker.unregister_host_buffer(b)
+    assert np.array_equal(got, want)
+
+
 def test_batch_ingest_matches_blocking_upload():
     """m3t_hip_cameras_set_ring + m3t_hip_cameras_upload_batch_async: the frames of all cameras for one ring slot as
     ONE page-locked block and one transfer, double-buffered against the tracking steps: the pose sequence of the
