@@ -215,6 +215,24 @@ class TextureModalityParams(C.Structure):
             self.standard_deviations[i] = float(v[i]) if i < len(v) else 0.0
 
 
+M3T_TEXTURE_DETECTOR_BUILTIN = 1
+
+
+class TextureDetectorParams(C.Structure):
+    """m3t_texture_detector_params: the built-in detector of a texture modality (m3t_texture_detector_params_default)."""
+    _fields_ = [("type", C.c_int), ("n_features", C.c_int), ("fast_threshold", C.c_int)]
+
+    def __init__(self, **kw):
+        super().__init__()
+        self.type = M3T_TEXTURE_DETECTOR_BUILTIN
+        self.n_features = 500
+        self.fast_threshold = 20
+        for k, v in kw.items():
+            if not hasattr(self, k):
+                raise AttributeError(k)
+            setattr(self, k, v)
+
+
 class TextureDataPoint(C.Structure):
     _fields_ = [("center_f_body", C.c_float * 3), ("center_f_camera", C.c_float * 3), ("center", C.c_float * 2),
                 ("correspondence_center", C.c_float * 2)]
@@ -419,6 +437,9 @@ _HIP_ONLY = {
     "texture_modality_model_occlusions": [C.c_int, C.c_int],
     "texture_modality_get_region_of_interest": [C.c_int, c_int_p, c_float_p, c_int_p],
     "texture_modality_set_features": [C.c_int, c_float_p, C.POINTER(C.c_uint8), C.c_int],
+    "texture_modality_set_detector": [C.c_int, C.POINTER(TextureDetectorParams)],
+    "texture_modality_get_features": [C.c_int, c_float_p, C.POINTER(C.c_uint8), C.c_int, c_int_p],
+    "texture_modality_get_focused_image": [C.c_int, C.POINTER(C.c_uint8), C.c_int, c_int_p, c_int_p],
     "texture_modality_get_points": [C.c_int, C.c_void_p, C.c_int, c_int_p],
     "texture_modality_get_keyframes": [C.c_int, c_int_p, c_int_p, c_int_p, c_float_p, C.c_int],
 }
@@ -447,7 +468,8 @@ def pose_ret(buf):
 
 
 _NEWER_ENTRY_POINTS = ("comm_set_reduce_callback", "get_step_kernel", "get_step_variant", "comm_get_allreduce_count", "comm_get_rank_count", "debug_log_checksum", "set_roi_ingest",
-                       "cameras_upload_batch_roi_async", "roi_get_status", "roi_get_unrecovered", "reserve_ingest_cus", "camera_slot_sync")
+                       "cameras_upload_batch_roi_async", "roi_get_status", "roi_get_unrecovered", "reserve_ingest_cus", "camera_slot_sync",
+                       "texture_modality_set_detector", "texture_modality_get_features", "texture_modality_get_focused_image")
 
 
 class CApi:

@@ -15,6 +15,7 @@
 
 #include "../../include/m3t_types.h"
 #include "m3t_texture.h"
+#include "m3t_features.h"
 
 // ---- per-line state, field-major: state[field * n_lines_max + line] ----------
 enum {
@@ -205,6 +206,19 @@ struct TextureModDev {
   float* data_points;               // [n_keyframes_max * 4096][TP_FLOATS]
   TextureStateDev* state;
   float* gradient_hessian;          // [6 + 36]
+};
+// The built-in feature detector of a texture modality (m3t_features.hip): one entry per modality that has one.  The
+// three images are dense ([height][width] of the last detection), sized for M3T_TEXTURE_FOCUSED_MAX squared.
+enum { DH_VALID = 0, DH_WIDTH, DH_HEIGHT, DH_ROI, DH_SCALE = DH_ROI + 4, DH_N, DH_WORDS = 12 };
+struct TextureDetectorDev {
+  int modality;            // index into the TextureModDev table
+  int n_features, fast_threshold, focused_image_size;
+  float radius;            // half the body's maximum diameter
+  uint32_t* features;      // the modality's feature block
+  uint8_t* focused;        // grey focused image
+  uint16_t* scores;        // FAST scores after suppression
+  uint16_t* boxes;         // 5 x 5 box sums
+  int* header;             // [DH_WORDS]: what the last detection saw (region of interest, scale, sizes, n)
 };
 
 // One rigid body with an unconstrained 6-dof root link (body2joint = I):

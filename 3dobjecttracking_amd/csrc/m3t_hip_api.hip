@@ -30,6 +30,7 @@
 #include "m3t_judge.hip"
 #include "m3t_opt.hip"
 #include "m3t_texture.hip"
+#include "m3t_features.hip"
 #include "m3t_compact.hip"
 #include "m3t_render.hip"
 #include "m3t_modelgen.hip"
@@ -324,6 +325,10 @@ struct TextureMod {  // TextureModality behind its feature detector (m3t_texture
   DevMem features, keyframe_points, keyframe_descriptors, data_points, state, gh;
   MappedRing uploads;  // set_features: the caller's features cross through page-locked blocks taken in turn
   TextureModDev dev{};
+  // the built-in detector (m3t_features.hip), when set_detector has named one: its parameters and its images
+  bool builtin = false;
+  m3t_texture_detector_params detector{};
+  DevMem focused, scores, boxes, detector_header;
 };
 enum ModalityKind { kRegionModality, kDepthModality, kTextureModality };
 struct ModalityRef {
@@ -453,6 +458,8 @@ struct m3t_hip_context {
   int n_corr_iterations = 5, n_update_iterations = 2;
   int fused_mode = 1;
   // device tables
+  DevMem d_detectors;   // TextureDetectorDev of the texture modalities with a built-in detector
+  int n_detectors = 0;
   DevMem d_cams, d_region, d_depth, d_texture, d_opts, d_poses, d_scratch_view;
   DevMem d_gh_sources, d_gh_all;  // m3t_hip_modalities_get_gradient_hessian
   int gh_sources_count = -1;
@@ -1694,6 +1701,28 @@ int UploadTables(Ctx* ctx) {
       HIPCHK(ctx->d_texture.alloc(t.size() * sizeof(TextureModDev)));
       HIPCHK(hipMemcpy(ctx->d_texture.p, t.data(), t.size() * sizeof(TextureModDev), hipMemcpyHostToDevice));
     }
+    std::vector<TextureDetectorDev> detectors;
+    for (size_t i = 0; i < ctx->texture_mods.size(); ++i) {
+      TextureMod& m = *ctx->texture_mods[i];
+      if (!m.builtin) continue;
+      TextureDetectorDev d{};
+      d.modality = int(i);
+      d.n_features = m.detector.n_features;
+      d.fast_threshold = m.detector.fast_threshold;
+      d.focused_image_size = m.p.focused_image_size;
+      d.radius = 0.5f * ctx->body_geometries[m.body]->maximum_body_diameter;
+      d.features = m.features.as<uint32_t>();
+      d.focused = m.focused.as<uint8_t>();
+      d.scores = m.scores.as<uint16_t>();
+      d.boxes = m.boxes.as<uint16_t>();
+      d.header = m.detector_header.as<int>();
+      detectors.push_back(d);
+    }
+    ctx->n_detectors = int(detectors.size());
+    if (!detectors.empty()) {
+      HIPCHK(ctx->d_detectors.alloc(detectors.size() * sizeof(TextureDetectorDev)));
+      HIPCHK(hipMemcpy(ctx->d_detectors.p, detectors.data(), detectors.size() * sizeof(TextureDetectorDev), hipMemcpyHostToDevice));
+    }
     // kinematic structures (m3t_links.hip) as soon as one optimizer is more than a free rigid body
     ctx->tree_mode = !ctx->texture_mods.empty();  // a texture modality: the general path, one launch per sub-step
     for (auto& o : ctx->optimizers) {
@@ -1867,7 +1896,11 @@ int CheckImages(Ctx* ctx) {
     const Camera& d = *ctx->cameras[m->camera];
     REQUIRE(d.has_image[d.current], M3T_ERR_NOT_SET_UP, "Set up depth camera first (no image uploaded)");
   }
-  for (auto& m : ctx->texture_mods) {  // (the colour frame is the caller's detector's; the kernels never read it)
+  for (auto& m : ctx->texture_mods) {  // (the colour frame is the detector's: the caller's, or the built-in one's)
+    if (m->builtin) {
+      const Camera& c = *ctx->cameras[m->camera];
+      REQUIRE(c.has_image[c.current], M3T_ERR_NOT_SET_UP, "Set up color camera first (no image uploaded)");
+    }
     if (!m->p.measure_occlusions) continue;
     const Camera& d = *ctx->cameras[m->depth_camera];
     REQUIRE(d.has_image[d.current], M3T_ERR_NOT_SET_UP, "Set up depth camera first (no image uploaded)");
@@ -1910,6 +1943,21 @@ int LaunchHistogram(Ctx* ctx, int iteration, bool initialize, bool behind_guarde
   return M3T_OK;
 }
 
+// DetectAndComputeCorrKeypoints (texture_modality.cpp:858-888) of the texture modalities with a built-in detector, on
+// the colour camera's current frame at the pose the device holds
+int LaunchTextureDetection(Ctx* ctx) {
+  const int n = ctx->n_detectors;
+  if (n == 0) return M3T_OK;
+  const dim3 bands(n, M3T_TEXTURE_FOCUSED_MAX / M3T_FEATURE_BAND);
+  const TextureDetectorDev* detectors = ctx->d_detectors.as<TextureDetectorDev>();
+  hipLaunchKernelGGL(texture_focus_kernel, bands, dim3(kFeatureThreads), 0, ctx->stream, detectors,
+                     ctx->d_texture.as<TextureModDev>(), ctx->cams_active, ctx->d_poses.as<float>());
+  hipLaunchKernelGGL(texture_fast_kernel, bands, dim3(kFeatureThreads), 0, ctx->stream, detectors);
+  hipLaunchKernelGGL(texture_describe_kernel, dim3(n), dim3(kDescribeThreads), 0, ctx->stream, detectors);
+  HIPCHK(hipGetLastError());
+  return M3T_OK;
+}
+
 // TextureModality::StartModality (decide = false) / CalculateResults (decide = true), behind their renderers
 int LaunchTextureKeyframes(Ctx* ctx, bool decide) {
   const int nt = int(ctx->texture_mods.size());
@@ -1923,6 +1971,10 @@ int LaunchTextureKeyframes(Ctx* ctx, bool decide) {
 int LaunchCorrespondences(Ctx* ctx, int iteration, int corr_iteration) {
   int nr = int(ctx->region_mods.size()), nd = int(ctx->depth_mods.size());
   if (const int nt = int(ctx->texture_mods.size())) {
+    if (corr_iteration == 0) {  // :334
+      const int r = LaunchTextureDetection(ctx);
+      if (r) return r;
+    }
     hipLaunchKernelGGL(texture_match_kernel, dim3(nt), dim3(M3T_TEXTURE_MATCH_THREADS), 0, ctx->stream,
                        ctx->d_texture.as<TextureModDev>(), ctx->cams_active, ctx->d_poses.as<float>(),
                        corr_iteration == 0 ? 1 : 0);
@@ -3605,6 +3657,8 @@ int m3t_hip_texture_modality_set_features(m3t_hip_context* ctx, int modality, co
   REQUIRE(n >= 0 && n <= M3T_MAX_TEXTURE_FEATURES, M3T_ERR_INVALID_ARGUMENT,
           "set_features: n must be in [0, " + std::to_string(M3T_MAX_TEXTURE_FEATURES) + "]");
   REQUIRE(n == 0 || (keypoints_xy && descriptors), M3T_ERR_INVALID_ARGUMENT, "set_features: null features");
+  REQUIRE(!m->builtin, M3T_ERR_UNSUPPORTED,
+          "set_features: the modality detects its features itself (texture_modality_set_detector(NULL) hands them back to the caller)");
   HIPCHK(hipSetDevice(ctx->device));
   // one block: {n, 0, 0, 0} | keypoints | descriptors; two copies on the context's stream, behind whatever it holds
   const size_t head_bytes = TF_HEADER_WORDS * 4 + size_t(n) * 8, descriptor_bytes = size_t(n) * m->p.descriptor_bytes;
@@ -3625,6 +3679,85 @@ int m3t_hip_texture_modality_set_features(m3t_hip_context* ctx, int modality, co
                           hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(m->uploads.Release(slot, ctx->stream));
   ctx->ingest.LaunchedUntracked();  // (copies on the compute stream behind no step event)
+  return M3T_OK;
+}
+int m3t_hip_texture_modality_set_detector(m3t_hip_context* ctx, int modality, const m3t_texture_detector_params* p) {
+  CHECK_CTX();
+  TextureMod* m = GetTexture(ctx, modality);
+  REQUIRE(m, M3T_ERR_INVALID_ARGUMENT, "bad texture modality id");
+  if (!p) {  // back to the caller's features (the images stay allocated: a later set_detector finds them)
+    if (m->builtin) ctx->tables_dirty = true;
+    m->builtin = false;
+    return M3T_OK;
+  }
+  REQUIRE(p->type == M3T_TEXTURE_DETECTOR_BUILTIN, M3T_ERR_INVALID_ARGUMENT, "set_detector: unknown detector type");
+  REQUIRE(p->n_features >= 1 && p->n_features <= M3T_MAX_TEXTURE_FEATURES, M3T_ERR_INVALID_ARGUMENT,
+          "set_detector: n_features must be in [1, " + std::to_string(M3T_MAX_TEXTURE_FEATURES) + "]");
+  REQUIRE(p->fast_threshold >= 0 && p->fast_threshold <= 255, M3T_ERR_INVALID_ARGUMENT,
+          "set_detector: fast_threshold must be in [0, 255]");
+  REQUIRE(m->p.descriptor_bytes == 32, M3T_ERR_UNSUPPORTED, "set_detector: the built-in detector writes 32-byte descriptors");
+  REQUIRE(m->p.focused_image_size <= M3T_TEXTURE_FOCUSED_MAX, M3T_ERR_UNSUPPORTED,
+          "set_detector: focused_image_size must not exceed " + std::to_string(M3T_TEXTURE_FOCUSED_MAX));
+  HIPCHK(hipSetDevice(ctx->device));
+  if (!m->focused.p) {
+    const size_t pixels = size_t(M3T_TEXTURE_FOCUSED_MAX) * M3T_TEXTURE_FOCUSED_MAX;
+    HIPCHK(m->focused.alloc(pixels));
+    HIPCHK(m->scores.alloc(pixels * 2));
+    HIPCHK(m->boxes.alloc(pixels * 2));
+    HIPCHK(m->detector_header.alloc(DH_WORDS * 4));
+    HIPCHK(hipMemset(m->detector_header.p, 0, DH_WORDS * 4));
+  }
+  m->detector = *p;
+  m->builtin = true;
+  ctx->tables_dirty = true;
+  return M3T_OK;
+}
+// what the last detection left (synchronous; for tests and for a caller who wants to look)
+static int ReadDetectorHeader(Ctx* ctx, TextureMod* m, int header[DH_WORDS]) {
+  HIPCHK(hipSetDevice(ctx->device));
+  HIPCHK(hipMemcpyAsync(header, m->detector_header.p, DH_WORDS * 4, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  return M3T_OK;
+}
+int m3t_hip_texture_modality_get_features(m3t_hip_context* ctx, int modality, float* keypoints_xy, uint8_t* descriptors,
+                                          int capacity, int* n_features) {
+  CHECK_CTX();
+  TextureMod* m = GetTexture(ctx, modality);
+  REQUIRE(m, M3T_ERR_INVALID_ARGUMENT, "bad texture modality id");
+  REQUIRE(n_features && capacity >= 0 && ((keypoints_xy && descriptors) || capacity == 0), M3T_ERR_INVALID_ARGUMENT,
+          "bad output buffer");
+  HIPCHK(hipSetDevice(ctx->device));
+  uint32_t header[TF_HEADER_WORDS];
+  HIPCHK(hipMemcpyAsync(header, m->features.p, sizeof(header), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  *n_features = int(header[0]);
+  const int n = std::min(int(header[0]), capacity);
+  if (n > 0) {
+    const uint8_t* block = m->features.as<uint8_t>();
+    HIPCHK(hipMemcpy(keypoints_xy, block + TF_HEADER_WORDS * 4, size_t(n) * 8, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(descriptors, block + (TF_HEADER_WORDS + 2 * M3T_TEXTURE_MAX_FEATURES) * 4,
+                     size_t(n) * m->p.descriptor_bytes, hipMemcpyDeviceToHost));
+  }
+  return M3T_OK;
+}
+int m3t_hip_texture_modality_get_focused_image(m3t_hip_context* ctx, int modality, uint8_t* pixels, int capacity, int* width,
+                                               int* height) {
+  CHECK_CTX();
+  TextureMod* m = GetTexture(ctx, modality);
+  REQUIRE(m, M3T_ERR_INVALID_ARGUMENT, "bad texture modality id");
+  REQUIRE(width && height && capacity >= 0 && (pixels || capacity == 0), M3T_ERR_INVALID_ARGUMENT, "bad output buffer");
+  REQUIRE(m->detector_header.p, M3T_ERR_NOT_SET_UP, "get_focused_image: the modality has had no built-in detector");
+  int header[DH_WORDS];
+  int r = ReadDetectorHeader(ctx, m, header);
+  if (r) return r;
+  *width = header[DH_WIDTH];
+  *height = header[DH_HEIGHT];
+  const size_t bytes = size_t(header[DH_WIDTH]) * size_t(header[DH_HEIGHT]);
+  if (pixels && bytes > 0) {
+    REQUIRE(size_t(capacity) >= bytes, M3T_ERR_INVALID_ARGUMENT,
+            "get_focused_image: the focused image has " + std::to_string(bytes) + " pixels");
+    HIPCHK(hipMemcpy(pixels, m->focused.p, bytes, hipMemcpyDeviceToHost));
+  }
   return M3T_OK;
 }
 int m3t_hip_texture_modality_get_points(m3t_hip_context* ctx, int modality, m3t_texture_data_point* out, int capacity,
@@ -4166,6 +4299,7 @@ int m3t_hip_start_modalities(m3t_hip_context* ctx, int iteration) {
     *static_cast<volatile unsigned*>(ctx->table_overflow_host) = 0u;
   }
   if ((r = RenderForModalities(ctx, true))) return r;  // start_modality_renderer_ptrs tracker.cpp:430-436
+  if ((r = LaunchTextureDetection(ctx))) return r;  // StartModality :319
   if ((r = LaunchTextureKeyframes(ctx, false))) return r;
   return LaunchHistogram(ctx, iteration, true);
 }

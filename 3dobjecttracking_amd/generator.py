@@ -428,6 +428,8 @@ class GeneratedTracker(host.Tracker):
         """DetectAndComputeCorrKeypoints (texture_modality.cpp:858-888) for every texture modality: the caller's
         detector on the focused image, the focus offset added (:884-887); no valid region of interest: no features"""
         for mod in self.texture_modalities:
+            if mod.detector is not None:  # the built-in detector: enqueued with the sub-step itself
+                continue
             focus = mod.RegionOfInterest()
             if focus is None:
                 mod.SetFeatures(np.zeros((0, 2), np.float32), np.zeros((0, mod.params.descriptor_bytes), np.uint8))
@@ -542,13 +544,18 @@ def GenerateConfiguredTracker(api, configfile_path, feature_detector=None, pass_
     (texture_modality.cpp:858-888): roi = (x, y, width, height) of the colour image, to be resized by scale; keypoints
     in the resized image, one row of 32 (ORB) or 64 (BRISK, FREAK) bytes per keypoint.  With pass_detector_params=True
     the callable is called with a fourth argument: the modality's descriptor_type and the orb_* / brisk_* / freak_*
-    members of its metafile, untouched, as a dict (they are also the modality object's .detector_params)."""
+    members of its metafile, untouched, as a dict (they are also the modality object's .detector_params).
+    feature_detector="builtin": every TextureModality gets the library's own detector on the device
+    (host.TextureModality.SetDetector; 32-byte descriptors whatever descriptor_type says -- it is not ORB), and
+    DetectFeatures does nothing for them."""
     path = str(configfile_path)
     d = cfg.read_yaml(path)
+    if isinstance(feature_detector, str) and feature_detector != "builtin":
+        raise ValueError("feature_detector=%r: a callable, \"builtin\" or None" % feature_detector)
     if d.get("TextureModality") and feature_detector is None:
         raise ValueError("Class TextureModality of %s needs the caller's feature detector: detection is outside the "
                          "tracking path this library replaces; pass feature_detector=callable(color_image, roi, scale) "
-                         "-> (focused_keypoints, descriptors)" % path)
+                         "-> (focused_keypoints, descriptors), or feature_detector=\"builtin\"" % path)
     for class_name in _REFUSED:
         if d.get(class_name):
             raise ValueError("Class %s of %s is outside the tracking path this library replaces" % (class_name, path))
@@ -644,7 +651,7 @@ def GenerateConfiguredTracker(api, configfile_path, feature_detector=None, pass_
             raise ValueError("TextureModality %s: descriptor_type %s is not a Hamming-norm descriptor (BRISK, FREAK or "
                              "ORB)" % (node["name"], descriptor_type))
         params = _modality_params(TextureModalityParams, node, path, _TEXTURE_KEYS)
-        params.descriptor_bytes = _DESCRIPTOR_TYPES[descriptor_type]
+        params.descriptor_bytes = 32 if feature_detector == "builtin" else _DESCRIPTOR_TYPES[descriptor_type]
         depth_camera = None
         if node.get("measure_occlusions"):
             depth_camera = _get(ob, "TextureModality", node["measure_occlusions"] | {"name": node["name"]},
@@ -660,6 +667,8 @@ def GenerateConfiguredTracker(api, configfile_path, feature_detector=None, pass_
         mod.color_camera = color_camera
         mod.detector_params = {k: v for k, v in m.items() if k.startswith(_DETECTOR_PREFIXES)}
         mod.detector_params["descriptor_type"] = descriptor_type
+        if feature_detector == "builtin":  # (the two members of the metafile that mean the same for this detector)
+            mod.SetDetector(n_features=int(m.get("orb_n_features", 500)), fast_threshold=int(m.get("orb_fast_threshold", 20)))
         texture_modalities.append(mod)
         modalities[node["name"]] = put("TextureModality", node, mod)
 
@@ -770,7 +779,7 @@ def GenerateConfiguredTracker(api, configfile_path, feature_detector=None, pass_
             raise ValueError("Object %s required by Tracker %s was not found" % (name, node["name"]))
         tracker.refiners.append(ob["Refiner"][name])
     tracker.texture_modalities = texture_modalities
-    tracker.feature_detector = feature_detector
+    tracker.feature_detector = None if feature_detector == "builtin" else feature_detector
     tracker.pass_detector_params = bool(pass_detector_params)
     tracker.objects = ob
     tracker.bodies = list(ob.get("Body", {}).values())

@@ -19,7 +19,7 @@ import numpy as np
 from . import _capi
 from ._capi import (DATA_LINE_DTYPE, DATA_POINT_DTYPE, M3T_MAX_TEXTURE_FEATURES, M3T_MAX_TEXTURE_KEYFRAMES,
                     TEXTURE_DATA_POINT_DTYPE, DepthModalityParams, DepthModelDesc, Intrinsics, M3TError,
-                    RegionModalityParams, RegionModelDesc, TextureModalityParams, fptr, iptr, pose_arg, pose_ret)
+                    RegionModalityParams, RegionModelDesc, TextureDetectorParams, TextureModalityParams, fptr, iptr, pose_arg, pose_ret)
 
 
 class Tracker:
@@ -572,6 +572,7 @@ class TextureModality(_Modality):
     def __init__(self, api, body, color_camera, silhouette_renderer, depth_camera=None, params=None, **kw):
         self.api = api
         self.params = params if params is not None else TextureModalityParams(**kw)
+        self.detector = None  # TextureDetectorParams while the built-in detector is set
         self.id = api.call("texture_modality_create", C.byref(self.params), body.id, color_camera.id,
                            silhouette_renderer.id, depth_camera.id if depth_camera is not None else -1)
 
@@ -596,6 +597,40 @@ class TextureModality(_Modality):
             raise ValueError("descriptors must have %d bytes per row" % self.params.descriptor_bytes)
         self.api.call("texture_modality_set_features", self.id, fptr(keypoints),
                       descriptors.ctypes.data_as(C.POINTER(C.c_uint8)), len(keypoints))
+
+    def SetDetector(self, params=None, builtin=True, **kw):
+        """the built-in detector (TextureDetectorParams or its fields as keywords): detection is then enqueued with
+        StartModalities and with every correspondence search, and SetFeatures is refused; SetDetector(builtin=False)
+        hands the features back to the caller"""
+        if not builtin:
+            self.detector = None
+            self.api.call("texture_modality_set_detector", self.id, None)
+            return
+        self.detector = params if params is not None else TextureDetectorParams(**kw)
+        self.api.call("texture_modality_set_detector", self.id, C.byref(self.detector))
+
+    def features(self):
+        """(keypoints n x 2 in full-image coordinates, descriptors n x descriptor_bytes) the modality holds; waits for
+        the stream"""
+        n = C.c_int()
+        self.api.call("texture_modality_get_features", self.id, None, None, 0, C.byref(n))
+        keypoints = np.zeros((max(n.value, 1), 2), np.float32)
+        descriptors = np.zeros((max(n.value, 1), self.params.descriptor_bytes), np.uint8)
+        self.api.call("texture_modality_get_features", self.id, fptr(keypoints),
+                      descriptors.ctypes.data_as(C.POINTER(C.c_uint8)), n.value, C.byref(n))
+        return keypoints[:n.value], descriptors[:n.value]
+
+    def focused_image(self):
+        """the grey focused image (height x width, uint8) of the last built-in detection, or None when it had no valid
+        region of interest; waits for the stream"""
+        width, height = C.c_int(), C.c_int()
+        self.api.call("texture_modality_get_focused_image", self.id, None, 0, C.byref(width), C.byref(height))
+        if width.value == 0 or height.value == 0:
+            return None
+        pixels = np.zeros((height.value, width.value), np.uint8)
+        self.api.call("texture_modality_get_focused_image", self.id, pixels.ctypes.data_as(C.POINTER(C.c_uint8)),
+                      pixels.size, C.byref(width), C.byref(height))
+        return pixels
 
     def SetFocusedFeatures(self, roi, scale, focused_keypoints, descriptors):
         """keypoints of the focused image: pt = roi.x + pt.x / scale in f32 (texture_modality.cpp:884-887)"""

@@ -242,7 +242,8 @@ int m3t_hip_depth_modality_model_occlusions(m3t_hip_context*, int modality_id, i
 int m3t_hip_depth_modality_use_silhouette_checking(m3t_hip_context*, int modality_id, int silhouette_renderer_id);
 
 /* ---- TextureModality behind its feature detector (texture_modality.cpp; line numbers below are that file's) ----------
- * Detection and description stay with the caller, as the reference delegates them to OpenCV (:858-888); everything
+ * Detection and description stay with the caller, as the reference delegates them to OpenCV (:858-888), unless
+ * texture_modality_set_detector names the built-in detector; everything
  * behind them runs on the device: keyframe reconstruction through the focused silhouette renderer with the two
  * occlusion tests (ComputeKeyframeData :933-1127), the brute-force 2-nearest-neighbour Hamming match with the ratio test
  * and the projection (CalculateCorrespondences :324-387), the Tukey-weighted g/H (:397-444, sums in the reference's
@@ -268,6 +269,21 @@ int m3t_hip_depth_modality_use_silhouette_checking(m3t_hip_context*, int modalit
  * texture_modality_get_keyframes: how many keyframes are held, keyframe_age_, the points per keyframe (oldest first;
  *   8 ints) and, unless points_xyz is NULL, the points themselves, keyframe after keyframe (capacity_points x 3 floats;
  *   M3T_ERR_INVALID_ARGUMENT if they do not fit).
+ * texture_modality_set_detector: the built-in detector (m3t_texture_detector_params, m3t_types.h) -- a detector of this
+ *   library's own, not ORB and not any OpenCV class: an integer bilinear focused image of the region of interest (no
+ *   equality with cv::resize), FAST-9 of 16, the n_features best corners in raster order, a direction out of 30, a
+ *   256-test binary descriptor of 32 bytes.  tests/feature_reference.py defines it bit for bit.  Detection is then
+ *   enqueued on the context's stream where the reference calls DetectAndComputeCorrKeypoints -- in start_modalities
+ *   (:319) and at corr_iteration 0 of every correspondence search (:334) -- at the pose the device holds, on the colour
+ *   camera's current frame, with no host read.  Refused (M3T_ERR_UNSUPPORTED) unless descriptor_bytes is 32 and
+ *   focused_image_size is at most 512; n_features in [1, 4096], fast_threshold in [0, 255].  A focused image with a
+ *   side above 512 pixels leaves the frame without features, like an invalid region of interest.  While a detector is
+ *   set, set_features on that modality is M3T_ERR_UNSUPPORTED and changes nothing; params = NULL hands the features
+ *   back to the caller.  Modalities with and without a detector may share a context.
+ * texture_modality_get_features / texture_modality_get_focused_image: the features the modality holds (n x 2 floats,
+ *   n rows of descriptor_bytes; *n_features is the number held, at most capacity are copied) and the grey focused image
+ *   of the last built-in detection (*width = *height = 0 when it had none; pixels may be NULL to ask for the size).
+ *   Both wait for the stream: for tests and for a caller who wants to look.
  * A context that holds a texture modality runs one launch per sub-step (get_step_kernel reports ""); reset_bodies,
  * reset_structures and a resetting judge_bodies on a body with a texture modality, ROI ingest, and a communicator or
  * reduce callback are M3T_ERR_UNSUPPORTED there. */
@@ -278,6 +294,11 @@ int m3t_hip_texture_modality_get_region_of_interest(m3t_hip_context*, int modali
                                                     int* valid);
 int m3t_hip_texture_modality_set_features(m3t_hip_context*, int modality_id, const float* keypoints_xy,
                                           const uint8_t* descriptors, int n);
+int m3t_hip_texture_modality_set_detector(m3t_hip_context*, int modality_id, const m3t_texture_detector_params* params);
+int m3t_hip_texture_modality_get_features(m3t_hip_context*, int modality_id, float* keypoints_xy, uint8_t* descriptors,
+                                          int capacity, int* n_features);
+int m3t_hip_texture_modality_get_focused_image(m3t_hip_context*, int modality_id, uint8_t* pixels, int capacity,
+                                               int* width, int* height);
 int m3t_hip_texture_modality_get_points(m3t_hip_context*, int modality_id, m3t_texture_data_point* out, int capacity,
                                         int* n_points);
 int m3t_hip_texture_modality_get_keyframes(m3t_hip_context*, int modality_id, int* n_keyframes, int* keyframe_age,

@@ -347,6 +347,32 @@ class TextureModality : public Modality {
   bool SetFeatures(const float* keypoints_xy, const uint8_t* descriptors, int n) {
     return c_->Step(m3t_hip_texture_modality_set_features(c_->get(), id_, keypoints_xy, descriptors, n));
   }
+  // the built-in detector (m3t_texture_detector_params_default); SetFeatures is refused while it is set
+  bool SetDetector(const m3t_texture_detector_params& params) {
+    return c_->Step(m3t_hip_texture_modality_set_detector(c_->get(), id_, &params));
+  }
+  bool ClearDetector() { return c_->Step(m3t_hip_texture_modality_set_detector(c_->get(), id_, nullptr)); }
+  // the features the modality holds: keypoints (x, y) in full-image coordinates and rows of descriptor_bytes
+  int features(std::vector<float>* keypoints_xy, std::vector<uint8_t>* descriptors, int descriptor_bytes = 32) const {
+    int n = 0;
+    c_->Check(m3t_hip_texture_modality_get_features(c_->get(), id_, nullptr, nullptr, 0, &n), "features");
+    keypoints_xy->assign(size_t(n) * 2 + 2, 0.0f);
+    descriptors->assign(size_t(n) * descriptor_bytes + 1, 0);
+    c_->Check(m3t_hip_texture_modality_get_features(c_->get(), id_, keypoints_xy->data(), descriptors->data(), n, &n),
+              "features");
+    keypoints_xy->resize(size_t(n) * 2);
+    descriptors->resize(size_t(n) * descriptor_bytes);
+    return n;
+  }
+  // the grey focused image of the last built-in detection, row after row; empty when it had no region of interest
+  std::vector<uint8_t> focused_image(int* width, int* height) const {
+    c_->Check(m3t_hip_texture_modality_get_focused_image(c_->get(), id_, nullptr, 0, width, height), "focused_image");
+    std::vector<uint8_t> pixels(size_t(*width) * size_t(*height));
+    if (!pixels.empty())
+      c_->Check(m3t_hip_texture_modality_get_focused_image(c_->get(), id_, pixels.data(), int(pixels.size()), width, height),
+                "focused_image");
+    return pixels;
+  }
   std::vector<m3t_texture_data_point> data_points() const {
     int n = 0;
     c_->Check(m3t_hip_texture_modality_get_points(c_->get(), id_, nullptr, 0, &n), "data_points");

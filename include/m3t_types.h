@@ -156,6 +156,16 @@ typedef struct m3t_texture_modality_params {
   float modeled_occlusion_threshold;
 } m3t_texture_modality_params;
 
+/* The built-in feature detector of a texture modality (m3t_hip_texture_modality_set_detector): a detector of this
+ * library's own -- FAST-9 corners, a direction out of 30, a 256-test binary descriptor of 32 bytes -- not one of the
+ * OpenCV classes the reference names, and not bit-compatible with any of them. */
+#define M3T_TEXTURE_DETECTOR_BUILTIN 1
+typedef struct m3t_texture_detector_params {
+  int type;           /* M3T_TEXTURE_DETECTOR_BUILTIN */
+  int n_features;     /* the best corners kept per frame, 1 .. M3T_MAX_TEXTURE_FEATURES */
+  int fast_threshold; /* of the segment test, 0 .. 255 */
+} m3t_texture_detector_params;
+
 /* Body geometry for the renderer-fed branches (body.h:46-60, body.cpp:196-250): a triangle mesh in
  * metres (geometry_unit_in_meter already applied), its pose in the body frame and the two ids the
  * silhouette renderer writes (body.h: body_id / region_id). */
@@ -333,6 +343,12 @@ static inline void m3t_texture_modality_params_default(m3t_texture_modality_para
   p->measured_occlusion_threshold = 0.03f;
   p->modeled_occlusion_radius = 0.01f;
   p->modeled_occlusion_threshold = 0.03f;
+}
+
+static inline void m3t_texture_detector_params_default(m3t_texture_detector_params* p) {
+  p->type = M3T_TEXTURE_DETECTOR_BUILTIN;
+  p->n_features = 500;
+  p->fast_threshold = 20;
 }
 
 #ifdef __cplusplus
