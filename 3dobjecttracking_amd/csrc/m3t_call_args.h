@@ -79,4 +79,21 @@ struct JudgeBodiesRenderArgs : Layout {
         renderer_pairs(Ints(2 * n_pairs)), reader_first(Ints(n_pairs + 1)), readers(Ints(n_readers)) {}
 };
 
+// The two calls that may restart texture modalities with a built-in detector (m3t_features.hip): the block of
+// ResetBodiesArgs / JudgeBodiesRenderArgs, segment for segment where that layout puts it, then [texture items: {detector,
+// texture modality, flag index or -1}, three ints each].  A call that lists no texture modality fills the old block.
+struct ResetBodiesTextureArgs : Layout {
+  Segment body_ids, region_ids, renderer_ids, renderer_pairs, poses, texture_items;
+  ResetBodiesTextureArgs(size_t n, size_t n_region, size_t n_render, bool with_poses, size_t n_texture)
+      : body_ids(Ints(n)), region_ids(Ints(n_region)), renderer_ids(Ints(n_render)), renderer_pairs(Ints(2 * n_render)),
+        poses(Poses(with_poses ? n : 0)), texture_items(Ints(3 * n_texture)) {}
+};
+struct JudgeBodiesTextureArgs : Layout {
+  Segment gt_poses, region_ids, region_body, region_first, renderer_pairs, reader_first, readers, texture_items;
+  JudgeBodiesTextureArgs(size_t n, size_t n_region, size_t n_pairs, size_t n_readers, size_t n_texture)
+      : gt_poses(Poses(n)), region_ids(Ints(n_region)), region_body(Ints(n_region)), region_first(Ints(n + 1)),
+        renderer_pairs(Ints(2 * n_pairs)), reader_first(Ints(n_pairs + 1)), readers(Ints(n_readers)),
+        texture_items(Ints(3 * n_texture)) {}
+};
+
 }  // namespace m3t_args

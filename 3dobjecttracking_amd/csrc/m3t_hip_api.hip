@@ -37,6 +37,11 @@
 #include "m3t_links.hip"
 #include "m3t_structures.hip"
 #include "m3t_ingest.hip"
+// the *_list_kernel forms of the texture kernels, behind every other kernel: no existing kernel moves in the code object
+#define M3T_TEXTURE_LIST_KERNELS
+#include "m3t_texture.hip"
+#include "m3t_features.hip"
+#undef M3T_TEXTURE_LIST_KERNELS
 
 static_assert(m3t_step::kBlockThreads == M3T_BLOCK_THREADS && m3t_step::kCompactThreads == M3T_COMPACT_THREADS &&
                   m3t_step::kSplitLanes == M3T_SPLIT_LANES && m3t_step::kSplitMaxParts == M3T_SPLIT_MAX_PARTS &&
@@ -2217,9 +2222,10 @@ int CheckListedIds(Ctx* ctx, const char* entry, const int* ids, int n, int limit
   }
   return M3T_OK;
 }
-// What the modalities of the listed bodies read: region modalities in table order, their start-modality renderers and
-// shared ColorHistograms (each once, in the order met), the cameras of all their modalities (as often as read).
-struct BodiesRead { std::vector<int> region_ids, renderer_ids, cameras, shared_ids; };
+// What the modalities of the listed bodies read: region and texture modalities in table order, their start-modality
+// renderers (the region modalities' first) and shared ColorHistograms (each once, in the order met), the cameras of all
+// their modalities (as often as read).
+struct BodiesRead { std::vector<int> region_ids, renderer_ids, cameras, shared_ids, texture_ids; };
 BodiesRead CollectReads(Ctx* ctx, const std::vector<char>& listed) {
   BodiesRead out;
   auto add_once = [](std::vector<int>* v, int id) {
@@ -2237,13 +2243,24 @@ BodiesRead CollectReads(Ctx* ctx, const std::vector<char>& listed) {
   }
   for (auto& m : ctx->depth_mods)
     if (listed[size_t(m->body)]) out.cameras.push_back(m->camera);
+  for (size_t i = 0; i < ctx->texture_mods.size(); ++i) {  // start_modality_renderer_ptrs :516-524
+    const TextureMod& m = *ctx->texture_mods[i];
+    if (!listed[size_t(m.body)]) continue;
+    out.texture_ids.push_back(int(i));
+    out.cameras.push_back(m.camera);
+    if (m.p.measure_occlusions) out.cameras.push_back(m.depth_camera);
+    add_once(&out.renderer_ids, m.silhouette_renderer);
+    add_once(&out.renderer_ids, m.dev.model_occlusions ? m.depth_renderer : -1);
+  }
   return out;
 }
-// A reset restarts a body's modalities from the host's side of the boundary; a texture modality's restart needs the
-// caller's detector on the frame at the new pose (StartModality :315-322), which no enqueued call can run.
-int RefuseTextureBodies(Ctx* ctx, const std::vector<char>& listed, const char* entry) {
+// A reset restarts a body's modalities from the host's side of the boundary; the restart of a texture modality that is
+// fed by the caller needs the caller's detector on the frame at the new pose (StartModality :315-322), which no enqueued
+// call can run.  One with the built-in detector (m3t_features.hip) is restarted on the device -- unless the entry
+// restarts none (with_detector_too: m3t_hip_reset_structures).
+int RefuseTextureBodies(Ctx* ctx, const std::vector<char>& listed, const char* entry, bool with_detector_too = false) {
   for (auto& m : ctx->texture_mods)
-    REQUIRE(!listed[size_t(m->body)], M3T_ERR_UNSUPPORTED,
+    REQUIRE(!listed[size_t(m->body)] || (m->builtin && !with_detector_too), M3T_ERR_UNSUPPORTED,
             std::string(entry) + ": a listed body has a texture modality (set the pose, set the features of the frame "
             "and call start_modalities)");
   return M3T_OK;
@@ -2290,6 +2307,38 @@ int LaunchStartRenderers(Ctx* ctx, const std::vector<int>& renderer_ids, const i
     largest = std::max(largest, ctx->renderers[size_t(id)]->image_size);
   }
   return LaunchRenderers(ctx, d_ids, int(renderer_ids.size()), d_pairs, int(renderer_ids.size()), largest);
+}
+// The texture items of a call ({detector, texture modality, flag index or -1}: m3t_call_args.h) for these texture
+// modalities, all of which have the built-in detector (RefuseTextureBodies).  flag_of: the flag index of a body, or null.
+std::vector<int> TextureItems(Ctx* ctx, const std::vector<int>& texture_ids, const std::vector<int>* flag_of) {
+  std::vector<int> detector_of(ctx->texture_mods.size(), -1);  // the detector table's order (UploadTables)
+  int n_detectors = 0;
+  for (size_t i = 0; i < ctx->texture_mods.size(); ++i)
+    if (ctx->texture_mods[i]->builtin) detector_of[i] = n_detectors++;
+  std::vector<int> items;
+  for (int id : texture_ids) {
+    items.push_back(detector_of[size_t(id)]);
+    items.push_back(id);
+    items.push_back(flag_of ? (*flag_of)[size_t(ctx->texture_mods[size_t(id)]->body)] : -1);
+  }
+  return items;
+}
+// StartModality (texture_modality.cpp:315-322) of the items of a call's argument block: detection on the colour
+// camera's current frame at the pose the device holds, then the keyframe, behind the call's renderers.  flags: the
+// judge's (an item runs iff its flag is set), or null (every item runs).
+int LaunchTextureRestart(Ctx* ctx, int n_items, const int* d_items, const int* d_flags) {
+  if (n_items == 0) return M3T_OK;
+  const dim3 bands(n_items, M3T_TEXTURE_FOCUSED_MAX / M3T_FEATURE_BAND);
+  const TextureDetectorDev* detectors = ctx->d_detectors.as<TextureDetectorDev>();
+  hipLaunchKernelGGL(texture_focus_list_kernel, bands, dim3(kFeatureThreads), 0, ctx->stream, detectors,
+                     ctx->d_texture.as<TextureModDev>(), ctx->cams_active, ctx->d_poses.as<float>(), d_items, d_flags);
+  hipLaunchKernelGGL(texture_fast_list_kernel, bands, dim3(kFeatureThreads), 0, ctx->stream, detectors, d_items, d_flags);
+  hipLaunchKernelGGL(texture_describe_list_kernel, dim3(n_items), dim3(kDescribeThreads), 0, ctx->stream, detectors,
+                     d_items, d_flags);
+  hipLaunchKernelGGL(texture_keyframe_list_kernel, dim3(n_items), dim3(M3T_TEXTURE_MATCH_THREADS), 0, ctx->stream,
+                     ctx->d_texture.as<TextureModDev>(), ctx->cams_active, ctx->d_poses.as<float>(), d_items, d_flags);
+  HIPCHK(hipGetLastError());
+  return M3T_OK;
 }
 Judge* GetJudge(Ctx* ctx, int id, const char* entry) {
   if (id >= 0 && id < int(ctx->judges.size())) return ctx->judges[size_t(id)].get();
@@ -4304,7 +4353,8 @@ int m3t_hip_start_modalities(m3t_hip_context* ctx, int iteration) {
   return LaunchHistogram(ctx, iteration, true);
 }
 // RBOTEvaluator::ResetBody (rbot_evaluator.cpp:334-342) for n bodies of the batch: their poses, the start-modality
-// renderers their modalities read, StartModality of their region modalities -- enqueued behind whatever the stream
+// renderers their modalities read, StartModality of their texture modalities (built-in detector only) and of their
+// region modalities, in the order of m3t_hip_start_modalities -- enqueued behind whatever the stream
 // holds, without reading poses back, waiting for the stream or uploading a table again (m3t_hip.h).
 int m3t_hip_reset_bodies(m3t_hip_context* ctx, const int* body_ids, const float* body2world_poses, int n, int iteration) {
   CHECK_CTX();
@@ -4324,10 +4374,15 @@ int m3t_hip_reset_bodies(m3t_hip_context* ctx, const int* body_ids, const float*
           "reset_bodies: a region modality of a listed body uses shared ColorHistograms (call start_modalities)");
   if ((r = RefuseRoiFrames(ctx, reads.cameras, "reset_bodies")) || (r = BeginEnqueued(ctx, true))) return r;
   const int n_region = int(reads.region_ids.size());
+  // (a call that lists no texture modality fills the block of ResetBodiesArgs, byte for byte as before)
+  const std::vector<int> texture_items = TextureItems(ctx, reads.texture_ids, nullptr);
+  const m3t_args::ResetBodiesTextureArgs texture_args(size_t(n), reads.region_ids.size(), reads.renderer_ids.size(),
+                                                      body2world_poses != nullptr, reads.texture_ids.size());
   const m3t_args::ResetBodiesArgs args(size_t(n), reads.region_ids.size(), reads.renderer_ids.size(), body2world_poses != nullptr);
   void *host = nullptr, *dev = nullptr;
   int slot = 0;
-  HIPCHK(ctx->reset_args.Acquire(args.bytes, &host, &dev, &slot));
+  HIPCHK(ctx->reset_args.Acquire(texture_items.empty() ? args.bytes : texture_args.bytes, &host, &dev, &slot));
+  m3t_args::PutInts(host, texture_args.texture_items, texture_items.data());
   m3t_args::PutInts(host, args.body_ids, body_ids);
   m3t_args::PutInts(host, args.region_ids, reads.region_ids.data());
   m3t_args::PutRenderers(host, args.renderer_ids, args.renderer_pairs, reads.renderer_ids.data());
@@ -4346,6 +4401,8 @@ int m3t_hip_reset_bodies(m3t_hip_context* ctx, const int* body_ids, const float*
   }
   for (int id : reads.region_ids) ctx->region_mods[id]->dev.first_iteration = iteration;
   if ((r = LaunchStartRenderers(ctx, reads.renderer_ids, args.renderer_ids.in<int>(dev), args.renderer_pairs.in<int>(dev))))
+    return r;
+  if ((r = LaunchTextureRestart(ctx, int(reads.texture_ids.size()), texture_args.texture_items.in<int>(dev), nullptr)))
     return r;
   if (n_region) {
     ScopedKernelTimer timer(ctx, 1);
@@ -4409,7 +4466,7 @@ int m3t_hip_reset_structures(m3t_hip_context* ctx, const int* optimizer_ids, int
       entries.push_back(e);
     }
   }
-  if ((r = RefuseTextureBodies(ctx, listed, "reset_structures"))) return r;
+  if ((r = RefuseTextureBodies(ctx, listed, "reset_structures", true))) return r;
   const BodiesRead reads = CollectReads(ctx, listed);
   for (auto& m : ctx->region_mods)
     REQUIRE(m->shared_histograms < 0 || listed[size_t(m->body)] ||
@@ -4596,6 +4653,7 @@ int m3t_hip_judge_bodies(m3t_hip_context* ctx, int judge, const float* gt_body2w
   BodiesRead reads;
   std::vector<int> region_ids, region_body_index, region_first(size_t(n) + 1, 0);  // the modalities grouped by listed body
   std::vector<int> render_pairs, reader_first, readers;  // judge_set_reset_renderers: what the device may render, and for whom
+  std::vector<int> texture_items;  // the texture modalities of the bodies a reset writes, flagged by their judge entry
   RenderLaunchShape render_shape{};
   if (ctx->judge_render_always < 0)  // once per context, like the other developer knobs
     ctx->judge_render_always = std::getenv("M3T_HIP_JUDGE_RENDER_ALWAYS") ? 1 : 0;
@@ -4630,7 +4688,12 @@ int m3t_hip_judge_bodies(m3t_hip_context* ctx, int judge, const float* gt_body2w
               "reset_iteration < 0 and call reset_bodies)");
       of_body[size_t(index_of[size_t(m.body)])].push_back(id);
     }
+    // (a texture modality's silhouette renderer is a start-modality renderer, :516-524)
+    REQUIRE(j->reset_renderers || reads.texture_ids.empty(), M3T_ERR_UNSUPPORTED,
+            "judge_bodies: a texture modality of a listed body reads a start-modality renderer (judge_set_reset_renderers "
+            "first, or judge with reset_iteration < 0 and call reset_bodies)");
     if ((r = RefuseRoiFrames(ctx, reads.cameras, "judge_bodies"))) return r;
+    texture_items = TextureItems(ctx, reads.texture_ids, &index_of);
     for (int i = 0; i < n; ++i) {
       for (int id : of_body[size_t(i)]) {
         region_ids.push_back(id);
@@ -4661,6 +4724,12 @@ int m3t_hip_judge_bodies(m3t_hip_context* ctx, int judge, const float* gt_body2w
             if (renderer >= 0 && (renderer == render_pairs[size_t(2 * p)] || renderer == render_pairs[size_t(2 * p + 1)]))
               reads_pair[size_t(index_of[size_t(m.body)])] = 1;
         }
+        for (int id : reads.texture_ids) {
+          const TextureMod& m = *ctx->texture_mods[size_t(id)];
+          for (int renderer : {m.silhouette_renderer, m.dev.model_occlusions ? m.depth_renderer : -1})
+            if (renderer >= 0 && (renderer == render_pairs[size_t(2 * p)] || renderer == render_pairs[size_t(2 * p + 1)]))
+              reads_pair[size_t(index_of[size_t(m.body)])] = 1;
+        }
         for (int i = 0; i < n; ++i)
           if (reads_pair[size_t(i)]) readers.push_back(i);
         reader_first.push_back(int(readers.size()));
@@ -4670,13 +4739,16 @@ int m3t_hip_judge_bodies(m3t_hip_context* ctx, int judge, const float* gt_body2w
   if ((r = BeginEnqueued(ctx, reset))) return r;
   const size_t n_region = region_ids.size();
   const size_t n_pairs = render_pairs.size() / 2;
-  // (a judge without judge_set_reset_renderers fills the block of JudgeBodiesArgs, byte for byte as before)
+  // (a judge without judge_set_reset_renderers fills the block of JudgeBodiesArgs, a call that restarts no texture
+  // modality that of JudgeBodiesRenderArgs, byte for byte as before)
+  const size_t n_texture = texture_items.size() / 3;
+  const m3t_args::JudgeBodiesTextureArgs texture_args(size_t(n), n_region, n_pairs, readers.size(), n_texture);
   const m3t_args::JudgeBodiesRenderArgs render_args(size_t(n), n_region, n_pairs, readers.size());
   const m3t_args::JudgeBodiesArgs plain_args(size_t(n), n_region);
   const m3t_args::JudgeBodiesArgs& args = plain_args;
   void *host = nullptr, *dev = nullptr;
   int slot = 0;
-  HIPCHK(j->args.Acquire(n_pairs ? render_args.bytes : plain_args.bytes, &host, &dev, &slot));
+  HIPCHK(j->args.Acquire(n_texture ? texture_args.bytes : n_pairs ? render_args.bytes : plain_args.bytes, &host, &dev, &slot));
   m3t_args::PutPoses(host, args.gt_poses, gt_body2world_poses);
   m3t_args::PutInts(host, args.region_ids, region_ids.data());
   m3t_args::PutInts(host, args.region_body, region_body_index.data());
@@ -4686,6 +4758,7 @@ int m3t_hip_judge_bodies(m3t_hip_context* ctx, int judge, const float* gt_body2w
     m3t_args::PutInts(host, render_args.reader_first, reader_first.data());
     m3t_args::PutInts(host, render_args.readers, readers.data());
   }
+  if (n_texture) m3t_args::PutInts(host, texture_args.texture_items, texture_items.data());  // (n_pairs > 0: behind the seven)
   const float* d_gt = args.gt_poses.in<float>(dev);
   const int *d_region_ids = args.region_ids.in<int>(dev), *d_region_body = args.region_body.in<int>(dev),
             *d_region_first = args.region_first.in<int>(dev);
@@ -4725,6 +4798,7 @@ int m3t_hip_judge_bodies(m3t_hip_context* ctx, int judge, const float* gt_body2w
                        dim3(M3T_BLOCK_THREADS), render_shape.lds, ctx->stream, ctx->d_renderers.as<RendererDev>(), d_pairs,
                        j->d_flags.as<int>(), d_reader_first, d_readers, render_always ? 1 : 0);
   }
+  if ((r = LaunchTextureRestart(ctx, int(n_texture), texture_args.texture_items.in<int>(dev), j->d_flags.as<int>()))) return r;
   if (n_region) {
     ScopedKernelTimer timer(ctx, 1);
     hipLaunchKernelGGL(region_histogram_flagged_kernel, dim3(unsigned(n_region)), dim3(M3T_BLOCK_THREADS), ctx->lds_hist,

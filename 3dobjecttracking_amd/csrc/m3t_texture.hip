@@ -4,6 +4,11 @@
 // renewal rule (:456-472).  Included by m3t_hip_api.hip behind m3t_kernels.hip (same translation unit: the pose math,
 // the renderer reads, occlusion_window_clear and the g/H chains).  One workgroup per texture modality in every kernel.
 
+// The file is included twice by m3t_hip_api.hip: the second time, with M3T_TEXTURE_LIST_KERNELS defined, it yields
+// texture_keyframe_list_kernel alone (at its end) -- behind every other kernel of the library, so that no existing kernel
+// moves in the code object.
+#ifndef M3T_TEXTURE_LIST_KERNELS
+
 typedef const __attribute__((address_space(4))) TextureModDev CTexture;
 typedef uint32_t v4u __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) v4u* LdsTile;
@@ -36,121 +41,12 @@ extern "C" {
 
 // ComputeKeyframeData :933-992 for every texture modality.  decide = 0: StartModality (:315-322).  decide = 1:
 // CalculateResults (:456-472) -- the age is counted and the renewal decided here, behind a block-uniform test.
+// (The body lives in m3t_texture_keyframe.inc: the list kernel below includes the same text behind its test, and this
+// kernel compiles to what it always was.)
 __global__ void __launch_bounds__(M3T_TEXTURE_MATCH_THREADS)
 texture_keyframe_kernel(const TextureModDev* mods, const CameraDev* cams, const float* body_poses, int decide) {
-  __shared__ int s_go, s_slot, s_modeled;
-  __shared__ int s_wave_counts[M3T_TEXTURE_MATCH_THREADS / kWave];
-  CTexture& m = *(CTexture*)(mods + blockIdx.x);
-  CCam& cam = *(CCam*)(cams + m.camera);
-  TextureStateDev* st = m.state;
-  const int tid = threadIdx.x;
-  const Affine b2c = mul_pose(load_pose(cam.world2camera), load_pose(body_poses + 16 * m.body));
-  if (tid == 0) {
-    int go = 1;
-    int head = st->head, held = st->n_keyframes;
-    if (decide) {
-      float o[3];
-      texture_orientation(b2c, o);
-      const float dot = (o[0] * st->orientation_last_keyframe[0] + o[1] * st->orientation_last_keyframe[1]) +
-                        o[2] * st->orientation_last_keyframe[2];
-      const float rotation_difference = float(acos(double(dot)));
-      const int age = st->keyframe_age + 1;
-      st->keyframe_age = age;
-      go = (rotation_difference > m.max_keyframe_rotation_difference || age > m.max_keyframe_age) ? 1 : 0;
-    }
-    if (go) {
-      if (held >= m.n_keyframes_max) {  // pop_front
-        head = (head + 1) % m.n_keyframes_max;
-        held -= 1;
-        st->head = head;
-        st->n_keyframes = held;
-      }
-      if (!renderer_body_visible(m.silhouette_renderer, m.silhouette_renderer_slot)) go = 0;  // :945
-    }
-    s_go = go;
-    s_slot = (head + held) % m.n_keyframes_max;
-    s_modeled = (m.model_occlusions && renderer_body_visible(m.depth_renderer, m.depth_renderer_slot)) ? 1 : 0;
-  }
-  __syncthreads();
-  if (!s_go) return;
-  const int slot = s_slot;
-  const bool modeled = s_modeled != 0;
-  const Affine c2b = inverse_pose(b2c);
-  const RendererDev& sr = *m.silhouette_renderer;
-  const FocusedCrop crop = renderer_crop(sr);
-  G<uint32_t> features = as_global(m.features);
-  const int n = (int)features[0];
-  const int words = m.descriptor_words;
-  G<float> xy = (G<float>)(features + TF_HEADER_WORDS);
-  G<uint32_t> descriptors = features + TF_HEADER_WORDS + 2 * M3T_TEXTURE_MAX_FEATURES;
-  GW<float> points = as_global_w(m.keyframe_points) + (size_t)slot * M3T_TEXTURE_MAX_FEATURES * 3;
-  GW<uint32_t> kept = as_global_w(m.keyframe_descriptors) + (size_t)slot * M3T_TEXTURE_MAX_FEATURES * words;
-  int count = 0;
-  for (int base = 0; base < n; base += M3T_TEXTURE_MATCH_THREADS) {
-    const int i = base + tid;
-    bool keep = false;
-    float px = 0.0f, py = 0.0f, pz = 0.0f;
-    if (i < n) {
-      // Reconstruct3DPoint :994-1023
-      const float cx = xy[2 * i], cy = xy[2 * i + 1];
-      const int u = f2i((cx - crop.corner_u) * crop.scale + 0.5f);
-      const int v = f2i((cy - crop.corner_v) * crop.scale + 0.5f);
-      if (u >= 0 && u <= crop.image_size - 1 && v >= 0 && v <= crop.image_size - 1 &&
-          (int)as_global(sr.silhouette_image)[(size_t)v * crop.image_size + u] == m.body_id) {
-        const unsigned short value = as_global(sr.depth_image)[(size_t)v * crop.image_size + u];
-        const float depth = renderer_depth(sr, value);
-        apply_pose(c2b, depth * (cx - cam.ppu) / cam.fu, depth * (cy - cam.ppv) / cam.fv, depth, px, py, pz);
-        keep = true;
-        if (m.measure_occlusions) {  // IsPointUnoccludedMeasured :1035-1081
-          CCam& dcam = *(CCam*)(cams + m.depth_camera);
-          const Affine b2dc = mul_pose(load_pose(dcam.world2camera), load_pose(body_poses + 16 * m.body));
-          float x, y, z;
-          apply_pose(b2dc, px, py, pz, x, y, z);
-          const float center_u = x * dcam.fu / z + dcam.ppu;
-          const float center_v = y * dcam.fv / z + dcam.ppv;
-          const float meter_to_pixel = dcam.fu / z;
-          const float diameter = 2.0f * m.measured_occlusion_radius * meter_to_pixel;
-          // (a negative or NaN diameter -- a point behind the depth camera -- has no window: the reference divides by a
-          // stride of zero there; the point is kept)
-          if (diameter >= 0.0f)
-            keep = occlusion_window_clear(dcam, center_u, center_v, diameter, z, 0.0f, m.measured_occlusion_threshold);
-        }
-        if (keep && modeled) {  // IsPointUnoccludedModeled :1083-1127
-          const RendererDev& dr = *m.depth_renderer;
-          float x, y, z;
-          apply_pose(b2c, px, py, pz, x, y, z);
-          const float meter_to_pixel = (cam.fu / z) * dr.state[RS_SCALE];
-          const float diameter = 2.0f * m.modeled_occlusion_radius * meter_to_pixel;
-          const float center_u = x * cam.fu / z + cam.ppu;
-          const float center_v = y * cam.fv / z + cam.ppv;
-          if (diameter >= 0.0f) {
-            const unsigned short min_value = modeled_window_min(dr, center_u, center_v, diameter);
-            keep = renderer_depth(dr, min_value) > z - m.modeled_occlusion_threshold;
-          }
-        }
-      }
-    }
-    int total;
-    const int rank = texture_stable_rank(keep, s_wave_counts, &total);
-    if (keep) {
-      const int at = count + rank;
-      points[3 * at] = px;
-      points[3 * at + 1] = py;
-      points[3 * at + 2] = pz;
-      for (int w = 0; w < words; ++w) kept[(size_t)at * words + w] = descriptors[(size_t)i * words + w];
-    }
-    count += total;
-  }
-  if (tid == 0) {
-    float o[3];
-    texture_orientation(b2c, o);
-    st->counts[slot] = count;
-    st->n_keyframes = st->n_keyframes + 1;
-    st->orientation_last_keyframe[0] = o[0];
-    st->orientation_last_keyframe[1] = o[1];
-    st->orientation_last_keyframe[2] = o[2];
-    st->keyframe_age = 0;
-  }
+  const unsigned modality_index = blockIdx.x;
+#include "m3t_texture_keyframe.inc"
 }
 
 }  // extern "C"
@@ -305,3 +201,28 @@ texture_gradient_hessian_kernel(const TextureModDev* mods, const CameraDev* cams
 }
 
 }  // extern "C"
+
+#else  // M3T_TEXTURE_LIST_KERNELS
+
+// Item `item` of an enqueued call's texture items ({detector, texture modality, flag index or -1}, three ints each) is
+// skipped iff the call has flags and the item's flag is 0 (m3t_features.hip, "StartModality ... an enqueued call lists")
+__device__ __forceinline__ bool texture_item_skipped(const int* items, const int* flags, int item) {
+  return flags != nullptr && !flags[items[3 * item + 2]];
+}
+
+extern "C" {
+
+// StartModality (:315-322, decide = 0) of the texture modalities an enqueued call lists, behind their renderers and
+// their detection: the item is blockIdx.x, skipped as in the list kernels of m3t_features.hip.
+__global__ void __launch_bounds__(M3T_TEXTURE_MATCH_THREADS)
+texture_keyframe_list_kernel(const TextureModDev* mods, const CameraDev* cams, const float* body_poses, const int* items,
+                             const int* flags) {
+  if (texture_item_skipped(items, flags, (int)blockIdx.x)) return;  // block-uniform
+  const int modality_index = items[3 * blockIdx.x + 1];
+  constexpr int decide = 0;
+#include "m3t_texture_keyframe.inc"
+}
+
+}  // extern "C"
+
+#endif  // M3T_TEXTURE_LIST_KERNELS

@@ -46,12 +46,32 @@ def rbot_pose_result(body2world_pose, body2world_pose_gt, translation_error_thre
     return t_err, r_err, 0.0 if lost else 1.0
 
 
-def evaluate_rbot_sequence(tracker, body, poses_gt, load_image, n_frames=None, reset_renderers=()):
+def judge_pose_result(body2world_pose, body2world_pose_gt, translation_error_threshold=F(0.05),
+                      rotation_error_threshold=F(5.0) * F(np.pi) / F(180.0)):
+    """rbot_pose_result in the arithmetic of the device judge (m3t_hip_judge_bodies, csrc/m3t_judge.hip), operation by
+    operation: f32 throughout, sums left to right, the cosine from the dot products of the rotation columns, acos in
+    double rounded to f32, the thresholds in f32.  rbot_pose_result leaves the order of its sums to numpy and differs
+    from the judge in the last digits; a loop judged on the host with this function reports what the same loop reports
+    when the device judges it, float for float."""
+    p, g = np.asarray(body2world_pose, F), np.asarray(body2world_pose_gt, F)
+    dx, dy, dz = F(p[0, 3] - g[0, 3]), F(p[1, 3] - g[1, 3]), F(p[2, 3] - g[2, 3])
+    t_err = F(np.sqrt(F(F(F(dx * dx) + F(dy * dy)) + F(dz * dz))))
+    d = [F(F(F(p[0, j] * g[0, j]) + F(p[1, j] * g[1, j])) + F(p[2, j] * g[2, j])) for j in range(3)]
+    c = F(F(F(F(d[0] + d[1]) + d[2]) - F(1.0)) * F(0.5))
+    with np.errstate(invalid="ignore"):
+        r_err = F(np.arccos(np.float64(c)))  # NaN for |c| > 1: the comparisons below are then false
+    lost = bool(t_err > F(translation_error_threshold)) or bool(r_err > F(rotation_error_threshold))
+    return float(t_err), float(r_err), 0.0 if lost else 1.0
+
+
+def evaluate_rbot_sequence(tracker, body, poses_gt, load_image, n_frames=None, reset_renderers=(),
+                           pose_result=rbot_pose_result):
     """RBOTEvaluator::EvaluateRunConfiguration (rbot_evaluator.cpp:174-210) for the main body: start on image 0
     at its ground truth, then cycle i tracks image i + 1 (the loader camera advances once per UpdateCameras),
     compares with the ground truth of image i + 1 and resets the body to it (ResetBody :334-342) whenever
     tracking is lost.  `load_image(k)` makes image k the cameras' current image.
-    Returns the per-frame results and their average (CalculateAverageResult :435-470)."""
+    Returns the per-frame results and their average (CalculateAverageResult :435-470).
+    pose_result: the judgement, rbot_pose_result or judge_pose_result."""
     n_frames = len(poses_gt) - 1 if n_frames is None else n_frames
 
     def reset(i):
@@ -72,7 +92,7 @@ def evaluate_rbot_sequence(tracker, body, poses_gt, load_image, n_frames=None, r
         dt = (time.perf_counter() - t0) * 1e6
         if not ok:
             raise RuntimeError("tracking step %d failed" % i)
-        t_err, r_err, success = rbot_pose_result(body.body2world_pose(), poses_gt[i + 1])
+        t_err, r_err, success = pose_result(body.body2world_pose(), poses_gt[i + 1])
         frames.append(dict(frame_index=i, translation_error=t_err, rotation_error=r_err,
                            tracking_success=success, complete_cycle=dt))
         if success == 0.0:
@@ -82,7 +102,8 @@ def evaluate_rbot_sequence(tracker, body, poses_gt, load_image, n_frames=None, r
     return frames, avg
 
 
-def evaluate_rbot_sequences(tracker, bodies, poses_gt_per_body, load_images, n_frames, judge_on_device=False):
+def evaluate_rbot_sequences(tracker, bodies, poses_gt_per_body, load_images, n_frames, judge_on_device=False,
+                            reset_renderers=False, pose_result=rbot_pose_result):
     """The loop of evaluate_rbot_sequence for N independent bodies in ONE context (HIP library): every body starts on
     image 0 at its own ground truth, cycle i tracks image i + 1 of all of them in one step, every body is judged
     against its own ground truth, and the lost ones -- those alone -- are reset with one Tracker.ResetBodies call
@@ -91,7 +112,10 @@ def evaluate_rbot_sequences(tracker, bodies, poses_gt_per_body, load_images, n_f
     Returns (per-body lists of per-frame results, per-body averages); complete_cycle is the time of the batch's step.
     judge_on_device (HIP library): the judgement and the reset are the device's (Tracker.CreateJudge, judge(gt, 0)
     behind every step): the loop makes no Sync() and reads no pose per frame, and the rows are read once after the last
-    frame.  complete_cycle is then the loop's wall time, the final read included, divided by its frames."""
+    frame.  complete_cycle is then the loop's wall time, the final read included, divided by its frames.
+    reset_renderers: the bodies' modalities read start-modality renderers (a texture modality's silhouette renderer):
+    the device judge may run them (Judge.set_reset_renderers); Tracker.ResetBodies runs them anyway.
+    pose_result: the host's judgement, rbot_pose_result or judge_pose_result (the device judge's arithmetic)."""
     for body, poses_gt in zip(bodies, poses_gt_per_body):
         body.set_body2world_pose(poses_gt[0])
     load_images(0)
@@ -101,6 +125,8 @@ def evaluate_rbot_sequences(tracker, bodies, poses_gt_per_body, load_images, n_f
     keys = ("translation_error", "rotation_error", "tracking_success", "complete_cycle")
     if judge_on_device:
         judge = tracker.CreateJudge(bodies, max(1, n_frames))
+        if reset_renderers:
+            judge.set_reset_renderers(True)
         t0 = time.perf_counter()
         for i in range(n_frames):
             load_images(i + 1)
@@ -126,7 +152,7 @@ def evaluate_rbot_sequences(tracker, bodies, poses_gt_per_body, load_images, n_f
             raise RuntimeError("tracking step %d failed" % i)
         lost = []
         for j, (body, poses_gt) in enumerate(zip(bodies, poses_gt_per_body)):
-            t_err, r_err, success = rbot_pose_result(body.body2world_pose(), poses_gt[i + 1])
+            t_err, r_err, success = pose_result(body.body2world_pose(), poses_gt[i + 1])
             frames[j].append(dict(frame_index=i, translation_error=t_err, rotation_error=r_err,
                                   tracking_success=success, complete_cycle=dt))
             if success == 0.0:
@@ -600,7 +626,8 @@ def evaluate_rbot_dataset(open_context, dataset_directory, external_directory, b
                           model_parameters=None, tikhonov_parameter_rotation=1000.0,
                           tikhonov_parameter_translation=30000.0, n_corr_iterations=7, n_update_iterations=2,
                           report=None, shard=(0, 1), batch=1, judge_on_device=False, sequence_occlusions=None,
-                          judge_occluder_on_own_pose=False):
+                          judge_occluder_on_own_pose=False, use_texture_modality=False, texture_parameters=None,
+                          detector_parameters=None):
     """RBOTEvaluator::SetUp + Evaluate for the region modality: for every (sequence,
     body) a tracker on `dataset/<body>/frames/<sequence>NNNN.png`, started at `dataset/poses_first.txt`, reset on
     loss, scored with the 5 cm / 5 degree criterion.  Bodies are `dataset/<body>/<body>.obj` in millimetres
@@ -622,7 +649,18 @@ def evaluate_rbot_dataset(open_context, dataset_directory, external_directory, b
     references both, two region modalities with ModelOcclusions, two rigid optimizers; the occluder follows
     `dataset/poses_second.txt`; the result's key is (sequence + "_modeled", body), the reference's title.  These runs
     go through evaluate_rbot_occlusion_sequences (HIP library, whatever `batch`): `batch` such runs -- 2 x batch
-    bodies, batch renderers -- share a context.  judge_occluder_on_own_pose: see there."""
+    bodies, batch renderers -- share a context.  judge_occluder_on_own_pose: see there.
+    use_texture_modality (HIP library; use_texture_modality_ of SetUpTracker :244-249, :274-283): every run also gets a
+    RendererGeometry with its body, a FocusedSilhouetteRenderer on its camera that references the body, and a
+    TextureModality(body, camera, silhouette) with `texture_parameters` and the built-in detector
+    (SetDetector(**detector_parameters)), behind the region modality in the optimizer's list.  A lost body is restarted
+    with its texture modality -- StartModalities with batch = 1, Tracker.ResetBodies in a batch, the device judge with
+    set_reset_renderers -- and the results are again those of batch = 1.  These runs are judged in the device judge's
+    arithmetic wherever the judgement sits (judge_pose_result on the host), so that the host-judged and the
+    device-judged loops report the same numbers float for float; runs without the argument keep rbot_pose_result.
+    ValueError: with the oracle's context, which
+    has no texture modality, and together with sequence_occlusions (the modelled-occlusion runs with texture are not
+    built)."""
     import os
 
     from . import config as cfg
@@ -630,12 +668,18 @@ def evaluate_rbot_dataset(open_context, dataset_directory, external_directory, b
     occlusions = list(sequence_occlusions) if sequence_occlusions is not None else [False] * len(sequence_names)
     if len(occlusions) != len(sequence_names):
         raise ValueError("sequence_occlusions needs one entry per sequence name")
+    texture = None
+    if use_texture_modality:
+        if any(occlusions):
+            raise ValueError("use_texture_modality together with sequence_occlusions is not supported: the runs with "
+                             "modelled occlusions have no texture modality")
+        texture = (dict(texture_parameters or {}), dict(detector_parameters or {}))
     if batch > 1 or judge_on_device or any(occlusions):
         return _evaluate_rbot_dataset_batched(open_context, dataset_directory, external_directory, body_names,
                                               sequence_names, n_frames, region_parameters, model_parameters,
                                               tikhonov_parameter_rotation, tikhonov_parameter_translation,
                                               n_corr_iterations, n_update_iterations, report, shard, max(1, batch),
-                                              judge_on_device, occlusions, judge_occluder_on_own_pose)
+                                              judge_on_device, occlusions, judge_occluder_on_own_pose, texture)
     poses_first = read_poses_rbot(os.path.join(dataset_directory, "poses_first.txt"), n_frames)
     region_parameters = dict(RBOT_REGION_PARAMETERS, **(region_parameters or {}))
     model_parameters = dict(RBOT_MODEL_PARAMETERS, **(model_parameters or {}))
@@ -654,8 +698,10 @@ def evaluate_rbot_dataset(open_context, dataset_directory, external_directory, b
             cfg.write_model_bin(model_path, True, model_parameters, body.body_data(), *model.views())
         camera = generator.LoaderColorCamera(api, os.path.join(dataset_directory, name, "frames"), RBOT_INTRINSICS,
                                              sequence, 0, 4)
-        modality = host.RegionModality(api, body, camera, model, **region_parameters)
-        host.Optimizer(api, body=body, modalities=[modality],
+        modalities = [host.RegionModality(api, body, camera, model, **region_parameters)]
+        if texture is not None:
+            modalities.append(_rbot_texture_modality(api, body, camera, *texture))
+        host.Optimizer(api, body=body, modalities=modalities,
                        tikhonov_parameter_rotation=tikhonov_parameter_rotation,
                        tikhonov_parameter_translation=tikhonov_parameter_translation)
         tracker = host.Tracker(api, n_corr_iterations, n_update_iterations)
@@ -665,7 +711,11 @@ def evaluate_rbot_dataset(open_context, dataset_directory, external_directory, b
             if not camera.UpdateImage():
                 raise RuntimeError("Could not read image from %s" % camera.image_path())
 
-        _, average = evaluate_rbot_sequence(tracker, body, poses_first, load_image, n_frames)
+        if texture is not None:
+            _, average = evaluate_rbot_sequence(tracker, body, poses_first, load_image, n_frames,
+                                                pose_result=judge_pose_result)
+        else:
+            _, average = evaluate_rbot_sequence(tracker, body, poses_first, load_image, n_frames)
         results[(sequence, name)] = average
         if report is not None:
             report(sequence + "_" + name, average)
@@ -674,13 +724,29 @@ def evaluate_rbot_dataset(open_context, dataset_directory, external_directory, b
     return results, overall
 
 
+def _rbot_texture_modality(api, body, camera, texture_parameters, detector_parameters):
+    """SetUpTracker's texture modality of the evaluated body (rbot_evaluator.cpp:244-249, :274-283) with the built-in
+    detector: a silhouette renderer of the run's own that draws and references the body alone"""
+    from . import host
+    if not getattr(api, "is_hip", True):
+        raise ValueError("use_texture_modality needs the HIP library: the oracle's context has no texture modality")
+    geometry = host.RendererGeometry(api)
+    geometry.AddBody(body)
+    silhouette = host.FocusedSilhouetteRenderer(api, geometry, camera, image_size=RBOT_FOCUSED_IMAGE_SIZE)
+    silhouette.AddReferencedBody(body)
+    modality = host.TextureModality(api, body, camera, silhouette, **texture_parameters)
+    modality.SetDetector(**detector_parameters)
+    return modality
+
+
 def _evaluate_rbot_dataset_batched(open_context, dataset_directory, external_directory, body_names, sequence_names,
                                    n_frames, region_parameters, model_parameters, tikhonov_parameter_rotation,
                                    tikhonov_parameter_translation, n_corr_iterations, n_update_iterations, report,
                                    shard, batch, judge_on_device=False, occlusions=None,
-                                   judge_occluder_on_own_pose=False):
+                                   judge_occluder_on_own_pose=False, texture=None):
     """evaluate_rbot_dataset with up to `batch` runs per context (same runs, same order, same results).  A context
-    holds runs of one kind: un-modelled ones, or runs with modelled occlusions."""
+    holds runs of one kind: un-modelled ones, or runs with modelled occlusions.  texture: (texture parameters, detector
+    parameters) of use_texture_modality, or None."""
     import os
 
     from . import config as cfg
@@ -734,7 +800,10 @@ def _evaluate_rbot_dataset_batched(open_context, dataset_directory, external_dir
                 renderer.AddReferencedBody(body)
                 renderer.AddReferencedBody(occluder)
                 modality.ModelOcclusions(renderer)
-            host.Optimizer(api, body=body, modalities=[modality],
+            modalities = [modality]
+            if texture is not None:
+                modalities.append(_rbot_texture_modality(api, body, camera, *texture))
+            host.Optimizer(api, body=body, modalities=modalities,
                            tikhonov_parameter_rotation=tikhonov_parameter_rotation,
                            tikhonov_parameter_translation=tikhonov_parameter_translation)
             if occluded:
@@ -758,6 +827,10 @@ def _evaluate_rbot_dataset_batched(open_context, dataset_directory, external_dir
             _, averages = evaluate_rbot_occlusion_sequences(
                 tracker, bodies, occluders, [poses_first] * len(chunk), [poses_second] * len(chunk), load_images,
                 n_frames, judge_on_device=judge_on_device, judge_occluder_on_own_pose=judge_occluder_on_own_pose)
+        elif texture is not None:
+            _, averages = evaluate_rbot_sequences(tracker, bodies, [poses_first] * len(chunk), load_images, n_frames,
+                                                  judge_on_device=judge_on_device, reset_renderers=True,
+                                                  pose_result=judge_pose_result)
         else:
             _, averages = evaluate_rbot_sequences(tracker, bodies, [poses_first] * len(chunk), load_images, n_frames,
                                                   judge_on_device=judge_on_device)

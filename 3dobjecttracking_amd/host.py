@@ -72,8 +72,10 @@ class Tracker:
 
     def ResetBodies(self, bodies, poses=None, iteration=0):
         """RBOTEvaluator::ResetBody (rbot_evaluator.cpp:334-352) for `bodies` alone, in one call (HIP library only):
-        their poses (None: the poses stay), the start-modality renderers their modalities read and
-        StartModality(iteration) of their region modalities; every other body keeps its state bit for bit"""
+        their poses (None: the poses stay), the start-modality renderers their modalities read, StartModality of their
+        texture modalities that have the built-in detector (detection on the current frame at the new pose, then a
+        keyframe; a texture modality fed through SetFeatures is refused) and StartModality(iteration) of their region
+        modalities; every other body keeps its state bit for bit"""
         ids = np.asarray([b.id for b in bodies], np.int32)
         flat = None
         if poses is not None:
@@ -138,8 +140,10 @@ class Tracker:
 
 class Judge:
     """m3t_hip_judge_*: RBOTEvaluator::CalculatePoseResults / YCBEvaluator::CalculatePoseResults of a list of bodies on
-    the device, with ResetBody of the bodies the device finds lost (reset_iteration >= 0).  `judge` is enqueued behind
-    the step like Tracker.ResetBodies and returns the index of the row it fills; nothing waits until `read`."""
+    the device, with ResetBody of the bodies the device finds lost (reset_iteration >= 0: their poses, their region
+    modalities and, after set_reset_renderers, their texture modalities with the built-in detector).  `judge` is
+    enqueued behind the step like Tracker.ResetBodies and returns the index of the row it fills; nothing waits until
+    `read`."""
 
     def __init__(self, api, bodies, n_rows_max):
         if "judge_create" not in api._fn:
@@ -173,8 +177,9 @@ class Judge:
 
     def set_reset_renderers(self, enable=True):
         """a resetting `judge` may run the start-modality renderers (ModelOcclusions / UseRegionChecking) that the
-        region modalities of the bodies it resets read -- each once, decided on the device, nothing when no body is
-        lost; off (the default): such bodies are refused"""
+        region modalities of the bodies it resets read, and those of their texture modalities (the silhouette renderer,
+        always) -- each once, decided on the device, nothing when no body is lost; off (the default): such bodies are
+        refused"""
         self.api.call("judge_set_reset_renderers", self.id, int(bool(enable)))
 
     def set_reset_target(self, body, target=None):

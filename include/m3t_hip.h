@@ -284,9 +284,11 @@ int m3t_hip_depth_modality_use_silhouette_checking(m3t_hip_context*, int modalit
  *   n rows of descriptor_bytes; *n_features is the number held, at most capacity are copied) and the grey focused image
  *   of the last built-in detection (*width = *height = 0 when it had none; pixels may be NULL to ask for the size).
  *   Both wait for the stream: for tests and for a caller who wants to look.
- * A context that holds a texture modality runs one launch per sub-step (get_step_kernel reports ""); reset_bodies,
- * reset_structures and a resetting judge_bodies on a body with a texture modality, ROI ingest, and a communicator or
- * reduce callback are M3T_ERR_UNSUPPORTED there. */
+ * A context that holds a texture modality runs one launch per sub-step (get_step_kernel reports "").  reset_bodies and
+ * a resetting judge_bodies restart the texture modalities of their bodies that have the built-in detector; on a body
+ * whose texture modality is fed by the caller they are M3T_ERR_UNSUPPORTED (the restart needs the caller's detector on
+ * the frame at the new pose), as is reset_structures on every body with a texture modality.  ROI ingest, and a
+ * communicator or reduce callback, are M3T_ERR_UNSUPPORTED in such a context. */
 int m3t_hip_texture_modality_create(m3t_hip_context*, const m3t_texture_modality_params*, int body_id, int color_camera_id,
                                     int silhouette_renderer_id, int depth_camera_id);
 int m3t_hip_texture_modality_model_occlusions(m3t_hip_context*, int modality_id, int depth_renderer_id);
@@ -347,13 +349,19 @@ int m3t_hip_start_modalities(m3t_hip_context*, int iteration);                  
  * call: what an evaluator of independent sequences does to the bodies it judged lost, and to no other.
  *   - body2world_poses (n x 16, column-major, or NULL: the poses stay): the listed bodies get these poses exactly as
  *     body_set_body2world_pose would give them; no other body's pose is touched.
- *   - the start-modality renderers the listed bodies' region modalities read are run (:338-339).
+ *   - the start-modality renderers the listed bodies' region and texture modalities read are run (:338-339); a
+ *     texture modality reads its silhouette renderer, and its depth renderer under model_occlusions.
+ *   - every TextureModality of a listed body that has the built-in detector (texture_modality_set_detector) does
+ *     TextureModality::StartModality (texture_modality.cpp:315-322): detection on the colour camera's current frame at
+ *     the new pose, then a keyframe from it (the oldest is popped when the ring is full; no keyframe is appended when
+ *     the body is not visible to the silhouette renderer) -- enqueued, with no host read, in the order of
+ *     start_modalities: renderers, detection, keyframes, histograms.
  *   - every RegionModality of a listed body does RegionModality::StartModality(iteration, 0)
  *     (region_modality.cpp:375-388): first_iteration = iteration, the histograms initialised from the current frame at
  *     the new pose with handle_occlusions = (n_unoccluded_iterations == 0).  DepthModalities: what start_modalities
  *     does for them (nothing to restart).
  * Everything else stays as it was, bit for bit: the other bodies' poses, histograms, first_iteration, line and point
- * state and the g/H of the last step.  The compact kernel's table-overflow latch (the step kernel with the LDS pair
+ * state, features, focused images, keyframes and the g/H of the last step.  The compact kernel's table-overflow latch (the step kernel with the LDS pair
  * table steps aside once histograms outgrow the table; start_modalities re-arms it) is left alone: it selects a
  * kernel, the poses do not depend on it.  State that follows a body's pose is left as body_set_body2world_pose +
  * start_modalities leave it: the next step's ROI rectangles start from a fresh snapshot of the poses, and a step
@@ -368,8 +376,9 @@ int m3t_hip_start_modalities(m3t_hip_context*, int iteration);                  
  *   M3T_ERR_UNSUPPORTED       a listed body in a structure of more than one link; a RegionModality of a listed body
  *                             that uses shared ColorHistograms (the reference's ResetBody leaves the shared object
  *                             half-updated there); ROI ingest: a camera read by a LISTED body's modality whose current
- *                             slot holds a rectangle only -- upload whole frames for those cameras alone.
- * A body without modalities only gets its pose. */
+ *                             slot holds a rectangle only -- upload whole frames for those cameras alone; a
+ *                             TextureModality of a listed body without the built-in detector.
+ * A body without modalities only gets its pose; one with a texture modality alone is restarted like any other. */
 int m3t_hip_reset_bodies(m3t_hip_context*, const int* body_ids, const float* body2world_poses /* n x 16, or NULL */,
                          int n, int iteration);
 /* RTBEvaluator::SetBodyAndJointPoses (examples/rtb_evaluator.cpp:809-858) followed by Tracker::StartModalities
@@ -422,8 +431,9 @@ int m3t_hip_reset_structures(m3t_hip_context*, const int* optimizer_ids, int n, 
  *     a k-d tree returns), sums in f64 in a fixed order: two calls on the same inputs return the same bits.
  * reset_iteration >= 0: every body found lost is reset as m3t_hip_reset_bodies(ids, gt poses, n, reset_iteration) resets
  * a list -- its pose becomes its ground truth, first_iteration of its region modalities becomes reset_iteration,
- * StartModality initialises their histograms -- and its was_reset is 1; every other body keeps its pose, histograms,
- * first_iteration, line / point state and g/H bit for bit.  reset_iteration < 0: nothing but the row is written.
+ * StartModality initialises their histograms, its texture modalities with the built-in detector detect and take a
+ * keyframe -- and its was_reset is 1; every other body keeps its pose, histograms, first_iteration, line / point
+ * state, features, keyframes and g/H bit for bit.  reset_iteration < 0: nothing but the row is written.
  * The call is enqueued on the context's stream behind whatever it holds, like reset_bodies: it reads no pose back, does
  * not wait for the stream and uploads no table; the ground-truth poses cross through a small ring of mapped host blocks
  * (the call may wait for the judgement four calls earlier).  A whole evaluated sequence can be queued without a wait
@@ -435,7 +445,8 @@ int m3t_hip_reset_structures(m3t_hip_context*, const int* optimizer_ids, int n, 
  *   M3T_ERR_UNSUPPORTED       with a reset: the refusals of reset_bodies (a structure of more than one link, shared
  *                             ColorHistograms, a frame slot that holds an ROI rectangle only), and a region modality
  *                             that reads a start-modality renderer (model_occlusions / use_region_checking: judge with
- *                             reset_iteration < 0 and call reset_bodies)
+ *                             reset_iteration < 0 and call reset_bodies) or a texture modality (which always reads
+ *                             one) unless judge_set_reset_renderers is on
  * After a resetting call the host's pose mirror does not vouch for these bodies (as after reset_bodies with poses).
  * judge_read waits for the event of the last requested row only and copies rows [first_row, first_row + n_rows) to
  * out[n_rows][n_bodies]; judge_clear starts the rows at 0 again.  judge_set_vertices (1 <= n <= 1 << 18 vertices of
@@ -474,9 +485,11 @@ int m3t_hip_reset_structures(m3t_hip_context*, const int* optimizer_ids, int n, 
  * Start-modality renderers (judge_set_reset_renderers; off by default, and then the refusal above stands).  With it on,
  * a resetting judge_bodies call has the contract of ONE reset_bodies call on the list of bodies the device finds lost:
  * the poses of all lost bodies are written; then every start-modality renderer that a region modality of at least one
- * lost body reads (model_occlusions: its depth renderer, use_region_checking: its silhouette renderer) is rendered
+ * lost body reads (model_occlusions: its depth renderer, use_region_checking: its silhouette renderer) or a texture
+ * modality of one (its silhouette renderer; model_occlusions: its depth renderer) is rendered
  * once, with the poses after all of the call's resets -- a renderer and its twin (same camera, geometry, referenced
- * bodies, depth range and image size) together; then StartModality of the lost bodies' region modalities runs.  Every
+ * bodies, depth range and image size) together; then StartModality of the lost bodies' texture modalities (detection,
+ * keyframes: the same flag word as the renderers and histograms test) and of their region modalities runs.  Every
  * other body, every renderer no lost body reads (unless its twin is read) and every renderer of a call in which nobody
  * is lost keep their images, crop, visibility and survivor counters bit for bit.  The host does not know whether a
  * renderer ran, so its "has rendered" mirror (renderer_get_images) is left as it was.  Only the two-launch form of the

@@ -524,7 +524,8 @@ class Tracker {
   }
   bool Sync() { return c_->Step(m3t_hip_sync(c_->get())); }
   // RBOTEvaluator::ResetBody (rbot_evaluator.cpp:334-352) for the listed bodies alone (m3t_hip_reset_bodies): their poses
-  // (empty: the poses stay), their start-modality renderers, StartModality(iteration) of their region modalities
+  // (empty: the poses stay), their start-modality renderers, StartModality of their texture modalities with the built-in
+  // detector (one fed by SetFeatures is refused) and StartModality(iteration) of their region modalities
   bool ResetBodies(const std::vector<const Body*>& bodies, const std::vector<Pose>& poses = {}, int iteration = 0) {
     if (!poses.empty() && poses.size() != bodies.size()) return false;
     std::vector<int> body_ids;
@@ -566,7 +567,8 @@ class Tracker {
     void SetAddOnly(int index, const Pose* geometry2body = nullptr) {
       c_->Check(m3t_hip_judge_set_add_only(c_->get(), id_, index, geometry2body ? geometry2body->data() : nullptr), "Judge");
     }
-    // a resetting JudgeBodies may run the start-modality renderers of the bodies it resets, decided on the device
+    // a resetting JudgeBodies may run the start-modality renderers of the bodies it resets, decided on the device; a
+    // body with a texture modality (built-in detector) needs this, its silhouette renderer being one of them
     void SetResetRenderers(bool enable = true) {
       c_->Check(m3t_hip_judge_set_reset_renderers(c_->get(), id_, enable ? 1 : 0), "Judge");
     }
