@@ -24,6 +24,7 @@
 #include "m3t_device.h"
 #include "m3t_view_rows.h"
 #include "m3t_step_plan.h"
+#include "m3t_render_plan.h"
 #include "m3t_call_args.h"
 #include "m3t_ingest_plan.h"
 #include "m3t_kernels.hip"
@@ -47,6 +48,7 @@ static_assert(m3t_step::kBlockThreads == M3T_BLOCK_THREADS && m3t_step::kCompact
                   m3t_step::kSplitLanes == M3T_SPLIT_LANES && m3t_step::kSplitMaxParts == M3T_SPLIT_MAX_PARTS &&
                   m3t_step::kMiscBytes == M3T_MISC_FLOATS * 4,
               "m3t_step_plan.h and m3t_device.h disagree");
+static_assert(m3t_render::kBlockThreads == M3T_BLOCK_THREADS, "m3t_render_plan.h and m3t_device.h disagree");
 
 namespace {
 
@@ -1393,45 +1395,26 @@ int UploadRendererTables(Ctx* ctx) {
   return M3T_OK;
 }
 
-// Renderings whose z-buffer fits the LDS of a CU: set-up + survivor list (32 slices of the triangle lists per renderer),
-// then one workgroup per renderer that rasterises the survivors in LDS and writes the images.  Larger ones: clear + crop,
-// rasterise into a z-buffer in memory, unpack.
-struct RenderLaunchShape {
-  int slices, bands;
-  size_t lds;  // of a resolve workgroup
-};
+// Which form a rendering takes and with what grid is decided in m3t_render_plan.h (host-checkable); what this file adds
+// is the one thing the plan cannot know: whether this device grants the resolve kernels their LDS.
+using m3t_render::RenderLaunchShape;
 RenderLaunchShape RenderShape(int n_pairs, int largest_image_size) {
-  // work spread: ~128 set-up workgroups (slices of the triangle lists) and ~256 resolve workgroups (bands of image
-  // rows, at least two rows each) per launch, whatever the number of renderings (measured on the reference's test
-  // scene, two pairs of twins, renderer-fed step: 32 bands 0.633 ms, 64: 0.624, 100: 0.611; 64 -> 128 slices: no
-  // change, 256: slower)
-  // (round 5: at 128 pairs -- the renderer-fed step of 64 objects -- 32 slices per pair were 4096 workgroups of 149
-  // VGPRs, one per CU at a time, each paying the projection and the matrix chain for two trips over its triangles:
-  // 131 us per set-up launch; 2 slices per pair = one workgroup per CU: 2.33 -> 1.64 ms per step,
-  // profiles/r05_render64_knobs.txt)
-  RenderLaunchShape s;
-  s.slices = std::min(128, std::max(2, 128 / std::max(1, n_pairs)));
-  s.bands = std::min(std::max(8, largest_image_size / 2), std::max(8, 256 / std::max(1, n_pairs)));
-  if (const char* e = std::getenv("M3T_HIP_RASTER_BANDS")) s.bands = std::max(1, std::atoi(e));    // developer overrides
-  if (const char* e = std::getenv("M3T_HIP_RASTER_SLICES")) s.slices = std::max(1, std::atoi(e));
-  const size_t band_rows = (size_t(largest_image_size) + s.bands - 1) / s.bands;
-  s.lds = band_rows * largest_image_size * 4 + (M3T_BLOCK_THREADS + 1 + 16 + 4 * M3T_BLOCK_THREADS) * 4;  // z-buffer band | prefix sums | wave totals | per-thread counts
-  return s;
+  return m3t_render::RenderShape(n_pairs, largest_image_size, m3t_render::ReadRenderOverrides());
 }
 // the two-launch form (z-buffer band in LDS) for a rendering of this shape?
 bool LdsRasterFits(Ctx* ctx, const RenderLaunchShape& shape, int largest_image_size) {
   if (ctx->lds_raster < 0) {  // once per context (= per device)
     ctx->lds_raster = 1;
-    if (std::getenv("M3T_HIP_NO_LDS_RASTER")) ctx->lds_raster = 0;
+    if (m3t_render::ReadRenderOverrides().no_lds_raster) ctx->lds_raster = 0;
     else
       for (const void* kernel : {reinterpret_cast<const void*>(focused_resolve_kernel),
                                  reinterpret_cast<const void*>(focused_resolve_flagged_kernel)})
-        if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
+        if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, int(m3t_render::kCuLdsBytes)) != hipSuccess) {
           (void)hipGetLastError();
           ctx->lds_raster = 0;
         }
   }
-  return ctx->lds_raster == 1 && largest_image_size > 0 && shape.lds <= size_t(160) * 1024;
+  return m3t_render::LdsRasterFits(shape, largest_image_size, ctx->lds_raster == 1);
 }
 int LaunchRenderers(Ctx* ctx, const int* which, int n_which, const int* pairs, int n_pairs, int largest_image_size) {
   if (n_which == 0) return M3T_OK;
@@ -1445,7 +1428,7 @@ int LaunchRenderers(Ctx* ctx, const int* which, int n_which, const int* pairs, i
     return M3T_OK;
   }
 #ifndef M3T_RASTER_SLICES
-#define M3T_RASTER_SLICES 32
+#define M3T_RASTER_SLICES m3t_render::kThreeLaunchSlices
 #endif
   hipLaunchKernelGGL(focused_clear_kernel, dim3(16, n_which), dim3(M3T_BLOCK_THREADS), 0, ctx->stream,
                      ctx->d_renderers.as<RendererDev>(), which, ctx->cams_active, ctx->d_poses.as<float>());

@@ -25,8 +25,15 @@ def _scene(api, image_size):
     return f, schauma, r
 
 
-@pytest.mark.parametrize("image_size", [200, 64, 333])  # 333: z-buffer in HBM instead of LDS
-def test_renderings_match_oracle(image_size):
+# 333: bands of 3 rows (one pair: 166 bands, ~14 KB of LDS each, 55 of them past the image's end) and scalar stores;
+# three launches: the same scenes with the z-buffer in memory (M3T_HIP_NO_LDS_RASTER, read at the context's first rendering)
+@pytest.mark.parametrize("image_size, three_launches",
+                         [pytest.param(200, False, id="200"), pytest.param(64, False, id="64"),
+                          pytest.param(333, False, id="333"), pytest.param(200, True, id="200-three-launches"),
+                          pytest.param(64, True, id="64-three-launches"), pytest.param(333, True, id="333-three-launches")])
+def test_renderings_match_oracle(image_size, three_launches, monkeypatch):
+    if three_launches:
+        monkeypatch.setenv("M3T_HIP_NO_LDS_RASTER", "1")
     out = []
     for api in (util.open_hip(), util.open_oracle()):
         f, schauma, r = _scene(api, image_size)
