@@ -434,6 +434,7 @@ _HIP_ONLY = {
     "judge_set_reset_target": [C.c_int, C.c_int, C.c_int],
     "vertices_diameter": [c_float_p, C.c_int, c_float_p],
     "texture_modality_create": [C.POINTER(TextureModalityParams), C.c_int, C.c_int, C.c_int, C.c_int],
+    "texture_modality_create_l2": [C.POINTER(TextureModalityParams), C.c_int, C.c_int, C.c_int, C.c_int],
     "texture_modality_model_occlusions": [C.c_int, C.c_int],
     "texture_modality_get_region_of_interest": [C.c_int, c_int_p, c_float_p, c_int_p],
     "texture_modality_set_features": [C.c_int, c_float_p, C.POINTER(C.c_uint8), C.c_int],
@@ -469,7 +470,8 @@ def pose_ret(buf):
 
 _NEWER_ENTRY_POINTS = ("comm_set_reduce_callback", "get_step_kernel", "get_step_variant", "comm_get_allreduce_count", "comm_get_rank_count", "debug_log_checksum", "set_roi_ingest",
                        "cameras_upload_batch_roi_async", "roi_get_status", "roi_get_unrecovered", "reserve_ingest_cus", "camera_slot_sync",
-                       "texture_modality_set_detector", "texture_modality_get_features", "texture_modality_get_focused_image")
+                       "texture_modality_set_detector", "texture_modality_get_features", "texture_modality_get_focused_image",
+                       "texture_modality_create_l2")
 
 
 class CApi:

@@ -220,6 +220,13 @@ struct TextureDetectorDev {
   uint16_t* boxes;         // 5 x 5 box sums
   int* header;             // [DH_WORDS]: what the last detection saw (region of interest, scale, sizes, n)
 };
+// A texture modality with L2-norm descriptors (m3t_texture_l2.hip): one entry per such modality.  Its TextureModDev
+// entry is like any other's, with descriptor_words the number of floats of a descriptor.
+struct TextureL2Dev {
+  int modality;            // index into the TextureModDev table
+  int reserved;
+  uint32_t* best;          // [n_keyframes_max][4096][3]: {d0, d1, i0} of every keyframe descriptor's last match
+};
 
 // One rigid body with an unconstrained 6-dof root link (body2joint = I):
 // Optimizer::CalculateOptimization specialised to dof = 6, J = I.

@@ -43,6 +43,8 @@
 #include "m3t_texture.hip"
 #include "m3t_features.hip"
 #undef M3T_TEXTURE_LIST_KERNELS
+// the matcher of L2-norm descriptors, behind those again
+#include "m3t_texture_l2.hip"
 
 static_assert(m3t_step::kBlockThreads == M3T_BLOCK_THREADS && m3t_step::kCompactThreads == M3T_COMPACT_THREADS &&
                   m3t_step::kSplitLanes == M3T_SPLIT_LANES && m3t_step::kSplitMaxParts == M3T_SPLIT_MAX_PARTS &&
@@ -336,6 +338,9 @@ struct TextureMod {  // TextureModality behind its feature detector (m3t_texture
   bool builtin = false;
   m3t_texture_detector_params detector{};
   DevMem focused, scores, boxes, detector_header;
+  // L2-norm descriptors (m3t_texture_l2.hip): descriptor_bytes / 4 floats a row, and the matcher's best-two scratch
+  bool l2 = false;
+  DevMem best;
 };
 enum ModalityKind { kRegionModality, kDepthModality, kTextureModality };
 struct ModalityRef {
@@ -466,6 +471,12 @@ struct m3t_hip_context {
   int fused_mode = 1;
   // device tables
   DevMem d_detectors;   // TextureDetectorDev of the texture modalities with a built-in detector
+  // With an L2 texture modality in the context: the Hamming modalities' TextureModDev entries alone (what
+  // texture_match_kernel is launched on) and the L2 modalities' TextureL2Dev table.  Without one, texture_match_kernel
+  // takes d_texture as it always did.
+  DevMem d_texture_hamming, d_texture_l2;
+  int n_texture_hamming = 0, n_texture_l2 = 0, l2_keyframes_max = 0;
+  size_t lds_texture_l2 = 0;
   int n_detectors = 0;
   DevMem d_cams, d_region, d_depth, d_texture, d_opts, d_poses, d_scratch_view;
   DevMem d_gh_sources, d_gh_all;  // m3t_hip_modalities_get_gradient_hessian
@@ -1689,6 +1700,40 @@ int UploadTables(Ctx* ctx) {
       HIPCHK(ctx->d_texture.alloc(t.size() * sizeof(TextureModDev)));
       HIPCHK(hipMemcpy(ctx->d_texture.p, t.data(), t.size() * sizeof(TextureModDev), hipMemcpyHostToDevice));
     }
+    {
+      std::vector<TextureModDev> hamming;
+      std::vector<TextureL2Dev> l2;
+      int words_max = 0;
+      ctx->l2_keyframes_max = 0;
+      for (size_t i = 0; i < ctx->texture_mods.size(); ++i) {
+        TextureMod& m = *ctx->texture_mods[i];
+        if (!m.l2) {
+          hamming.push_back(m.dev);
+          continue;
+        }
+        TextureL2Dev d{};
+        d.modality = int(i);
+        d.best = m.best.as<uint32_t>();
+        l2.push_back(d);
+        words_max = std::max(words_max, m.dev.descriptor_words);
+        ctx->l2_keyframes_max = std::max(ctx->l2_keyframes_max, m.dev.n_keyframes_max);
+      }
+      ctx->n_texture_l2 = int(l2.size());
+      ctx->n_texture_hamming = int(hamming.size());
+      if (!l2.empty()) {
+        HIPCHK(ctx->d_texture_l2.alloc(l2.size() * sizeof(TextureL2Dev)));
+        HIPCHK(hipMemcpy(ctx->d_texture_l2.p, l2.data(), l2.size() * sizeof(TextureL2Dev), hipMemcpyHostToDevice));
+        if (!hamming.empty()) {
+          HIPCHK(ctx->d_texture_hamming.alloc(hamming.size() * sizeof(TextureModDev)));
+          HIPCHK(hipMemcpy(ctx->d_texture_hamming.p, hamming.data(), hamming.size() * sizeof(TextureModDev), hipMemcpyHostToDevice));
+        }
+        ctx->lds_texture_l2 = texture_l2_lds_bytes(words_max);
+        // (the attribute belongs to the function, not to this context: the widest descriptor any context can hold)
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(texture_match_l2_kernel),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   int(texture_l2_lds_bytes(M3T_TEXTURE_L2_MAX_FLOATS))));
+      }
+    }
     std::vector<TextureDetectorDev> detectors;
     for (size_t i = 0; i < ctx->texture_mods.size(); ++i) {
       TextureMod& m = *ctx->texture_mods[i];
@@ -1963,9 +2008,25 @@ int LaunchCorrespondences(Ctx* ctx, int iteration, int corr_iteration) {
       const int r = LaunchTextureDetection(ctx);
       if (r) return r;
     }
-    hipLaunchKernelGGL(texture_match_kernel, dim3(nt), dim3(M3T_TEXTURE_MATCH_THREADS), 0, ctx->stream,
-                       ctx->d_texture.as<TextureModDev>(), ctx->cams_active, ctx->d_poses.as<float>(),
-                       corr_iteration == 0 ? 1 : 0);
+    const int match = corr_iteration == 0 ? 1 : 0;
+    if (ctx->n_texture_l2 == 0) {
+      hipLaunchKernelGGL(texture_match_kernel, dim3(nt), dim3(M3T_TEXTURE_MATCH_THREADS), 0, ctx->stream,
+                         ctx->d_texture.as<TextureModDev>(), ctx->cams_active, ctx->d_poses.as<float>(), match);
+    } else {
+      // the Hamming matcher sees the Hamming modalities alone; the L2 modalities' match is tiled over keyframes and
+      // queries (texture_match_l2_kernel, which finds on the device what it has to do) with the ratio test, the data
+      // points and the projection behind it -- at corr_iteration > 0 the projection alone
+      if (ctx->n_texture_hamming)
+        hipLaunchKernelGGL(texture_match_kernel, dim3(ctx->n_texture_hamming), dim3(M3T_TEXTURE_MATCH_THREADS), 0, ctx->stream,
+                           ctx->d_texture_hamming.as<TextureModDev>(), ctx->cams_active, ctx->d_poses.as<float>(), match);
+      const TextureL2Dev* l2 = ctx->d_texture_l2.as<TextureL2Dev>();
+      if (match)
+        hipLaunchKernelGGL(texture_match_l2_kernel, dim3(ctx->n_texture_l2, ctx->l2_keyframes_max * kL2QueryTiles),
+                           dim3(M3T_TEXTURE_MATCH_THREADS), ctx->lds_texture_l2, ctx->stream, l2,
+                           ctx->d_texture.as<TextureModDev>());
+      hipLaunchKernelGGL(texture_collect_l2_kernel, dim3(ctx->n_texture_l2), dim3(M3T_TEXTURE_MATCH_THREADS), 0, ctx->stream,
+                         l2, ctx->d_texture.as<TextureModDev>(), ctx->cams_active, ctx->d_poses.as<float>(), match);
+    }
     HIPCHK(hipGetLastError());
   }
   if (nr) {
@@ -3571,8 +3632,8 @@ int m3t_hip_depth_modality_use_silhouette_checking(m3t_hip_context* ctx, int mod
 }
 
 // ---- TextureModality behind its feature detector (m3t_texture.hip) --------------------------------------------------
-int m3t_hip_texture_modality_create(m3t_hip_context* ctx, const m3t_texture_modality_params* p, int body, int color_camera,
-                                    int silhouette_renderer, int depth_camera) {
+static int CreateTextureModality(m3t_hip_context* ctx, const m3t_texture_modality_params* p, int body, int color_camera,
+                                 int silhouette_renderer, int depth_camera, bool l2) {
   CHECK_CTX();
   REQUIRE(p, M3T_ERR_INVALID_ARGUMENT, "null params");
   REQUIRE(body >= 0 && body < int(ctx->body_poses.size() / 16), M3T_ERR_INVALID_ARGUMENT, "bad body id");
@@ -3581,8 +3642,14 @@ int m3t_hip_texture_modality_create(m3t_hip_context* ctx, const m3t_texture_moda
   if (p->measure_occlusions)
     REQUIRE(depth_camera >= 0 && depth_camera < int(ctx->cameras.size()) && ctx->cameras[depth_camera]->is_depth,
             M3T_ERR_INVALID_ARGUMENT, "measure_occlusions needs a depth camera");
-  REQUIRE(p->descriptor_bytes == 32 || p->descriptor_bytes == 64, M3T_ERR_INVALID_ARGUMENT,
-          "descriptor_bytes must be 32 (ORB) or 64 (BRISK, FREAK): Hamming-norm descriptors only");
+  if (l2)
+    REQUIRE(p->descriptor_bytes % 16 == 0 && p->descriptor_bytes >= 4 * M3T_TEXTURE_L2_MIN_FLOATS &&
+                p->descriptor_bytes <= 4 * M3T_TEXTURE_L2_MAX_FLOATS,
+            M3T_ERR_INVALID_ARGUMENT,
+            "descriptor_bytes must be 4 * D for D floats a descriptor, a multiple of 16 in [16, 1024] (SIFT: 512)");
+  else
+    REQUIRE(p->descriptor_bytes == 32 || p->descriptor_bytes == 64, M3T_ERR_INVALID_ARGUMENT,
+            "descriptor_bytes must be 32 (ORB) or 64 (BRISK, FREAK): Hamming-norm descriptors only");
   REQUIRE(p->n_keyframes >= 1 && p->n_keyframes <= M3T_MAX_TEXTURE_KEYFRAMES && p->n_standard_deviations >= 1 &&
               p->n_standard_deviations <= M3T_MAX_SCALES && p->focused_image_size >= 1,
           M3T_ERR_INVALID_ARGUMENT, "bad texture modality parameters");
@@ -3634,6 +3701,10 @@ int m3t_hip_texture_modality_create(m3t_hip_context* ctx, const m3t_texture_moda
   HIPCHK(m->data_points.alloc(slots * TP_FLOATS * 4));
   HIPCHK(m->state.alloc(sizeof(TextureStateDev)));
   HIPCHK(m->gh.alloc(42 * 4));
+  if (l2) {
+    m->l2 = true;
+    HIPCHK(m->best.alloc(slots * 3 * 4));
+  }
   HIPCHK(hipMemset(m->features.p, 0, TF_HEADER_WORDS * 4));
   HIPCHK(hipMemset(m->state.p, 0, m->state.bytes));
   HIPCHK(hipMemset(m->gh.p, 0, m->gh.bytes));
@@ -3647,6 +3718,14 @@ int m3t_hip_texture_modality_create(m3t_hip_context* ctx, const m3t_texture_moda
   ctx->modalities.push_back({kTextureModality, int(ctx->texture_mods.size()) - 1});
   ctx->tables_dirty = true;
   return int(ctx->modalities.size()) - 1;
+}
+int m3t_hip_texture_modality_create(m3t_hip_context* ctx, const m3t_texture_modality_params* p, int body, int color_camera,
+                                    int silhouette_renderer, int depth_camera) {
+  return CreateTextureModality(ctx, p, body, color_camera, silhouette_renderer, depth_camera, false);
+}
+int m3t_hip_texture_modality_create_l2(m3t_hip_context* ctx, const m3t_texture_modality_params* p, int body, int color_camera,
+                                       int silhouette_renderer, int depth_camera) {
+  return CreateTextureModality(ctx, p, body, color_camera, silhouette_renderer, depth_camera, true);
 }
 int m3t_hip_texture_modality_model_occlusions(m3t_hip_context* ctx, int modality, int renderer) {
   CHECK_CTX();
@@ -3722,6 +3801,8 @@ int m3t_hip_texture_modality_set_detector(m3t_hip_context* ctx, int modality, co
     m->builtin = false;
     return M3T_OK;
   }
+  REQUIRE(!m->l2, M3T_ERR_UNSUPPORTED,
+          "set_detector: the built-in detector writes 32-byte binary descriptors, the modality matches rows of floats with the L2 norm");
   REQUIRE(p->type == M3T_TEXTURE_DETECTOR_BUILTIN, M3T_ERR_INVALID_ARGUMENT, "set_detector: unknown detector type");
   REQUIRE(p->n_features >= 1 && p->n_features <= M3T_MAX_TEXTURE_FEATURES, M3T_ERR_INVALID_ARGUMENT,
           "set_detector: n_features must be in [1, " + std::to_string(M3T_MAX_TEXTURE_FEATURES) + "]");

@@ -1,7 +1,8 @@
 // m3t_texture.h -- the arithmetic of TextureModality (M3T/src/texture_modality.cpp) that host and device share:
 // the focused region of interest (:890-931), the Tukey weight (:424-427, 1231-1237), the best-two update and the ratio
-// test of the brute-force matcher (:349-367) and the products of one data point (:407-440).  Free of device-only
-// constructs so that tests/cpp/texture_check.cpp runs it on the host.  f32 left to right, no contraction (the library
+// test of the brute-force matcher (:349-367) -- for Hamming-norm descriptors and, further down, for L2-norm ones -- and
+// the products of one data point (:407-440).  Free of device-only constructs so that tests/cpp/texture_check.cpp and
+// tests/cpp/texture_l2_check.cpp run it on the host.  f32 left to right, no contraction (the library
 // and the check are built with -ffp-contract=off), int() truncating.
 #pragma once
 #include <float.h>
@@ -100,6 +101,87 @@ M3T_TEX_FN void m3t_tex_best2_update(m3t_tex_best2* b, int distance, int index) 
 M3T_TEX_FN bool m3t_tex_ratio_keeps(const m3t_tex_best2* b, float threshold) {
   if (b->d1 == INT32_MAX) return false;  // knn_match.size() < 2
   return !((float)b->d0 / (float)b->d1 >= threshold);
+}
+
+// ---- L2-norm descriptors (SIFT, DAISY: cv::BFMatcher(cv::NORM_L2), :794-796) -------------------------------------------
+// A descriptor is D floats, D a multiple of 4 in [4, 256].  The distance is std::sqrt(normL2Sqr(q, t)) of OpenCV's
+// batchDistL2_32f with the order of the sum fixed: s = 0, then s = s + (q[k] - t[k]) * (q[k] - t[k]) for k = 0 .. D - 1 in
+// ascending order, every operation rounded to f32, no contraction; the distance is sqrtf(s), correctly rounded.
+#define M3T_TEXTURE_L2_MIN_FLOATS 4
+#define M3T_TEXTURE_L2_MAX_FLOATS 256    /* SIFT: 128; DAISY: (3 * 4 + 1) * 8 = 104, with OpenCV's defaults (3 * 8 + 1) * 8 = 200 */
+#define M3T_TEXTURE_L2_QUERY_TILE 64     /* query descriptors per workgroup of texture_match_l2_kernel: a lane each */
+#define M3T_TEXTURE_L2_TRAIN_TILE 32     /* train descriptors per LDS tile: a quarter for each of the four waves */
+#define M3T_TEXTURE_L2_ROWS 8            /* train rows a thread carries at a time */
+
+M3T_TEX_FN float m3t_tex_l2_squared(const float* q, const float* t, int n_floats) {
+  float s = 0.0f;
+  for (int k = 0; k < n_floats; ++k) {
+    const float e = q[k] - t[k];
+    s = s + e * e;
+  }
+  return s;
+}
+M3T_TEX_FN float m3t_tex_l2_distance(const float* q, const float* t, int n_floats) {
+  return sqrtf(m3t_tex_l2_squared(q, t, n_floats));
+}
+
+// The best two of an L2 match.  The comparison is on the distances (the sqrtf values), not on the sums: two sums that
+// differ can round to one distance, and then the lower index ranks first.  A NaN distance satisfies no `<` and never
+// enters; that leaves NaN free to mark "no entry yet" (+inf is a distance like any other).
+struct m3t_tex_best2f {
+  float d0, d1;  // distances; NaN: no entry yet
+  int i0;        // train index of the best
+};
+M3T_TEX_FN void m3t_tex_best2f_init(m3t_tex_best2f* b) {
+  b->d0 = b->d1 = NAN;
+  b->i0 = -1;
+}
+M3T_TEX_FN void m3t_tex_best2f_update(m3t_tex_best2f* b, float distance, int index) {
+  if (distance != distance) return;
+  if (b->d0 != b->d0 || distance < b->d0) {
+    b->d1 = b->d0;
+    b->d0 = distance;
+    b->i0 = index;
+  } else if (b->d1 != b->d1 || distance < b->d1) {
+    b->d1 = distance;
+  }
+}
+// The same update from the sum s, with the square root taken only where it can matter.  s1 is the sum behind d1 (NaN
+// while there is no second entry), s0 the sum behind d0.  sqrtf is monotone: s >= s1 gives sqrtf(s) >= d1 >= d0, and
+// such a candidate displaces nothing.  Every other candidate (a NaN sum among them) takes the update above.
+struct m3t_tex_best2s {
+  m3t_tex_best2f b;
+  float s0, s1;
+};
+M3T_TEX_FN void m3t_tex_best2s_init(m3t_tex_best2s* b) {
+  m3t_tex_best2f_init(&b->b);
+  b->s0 = b->s1 = NAN;
+}
+M3T_TEX_FN void m3t_tex_best2s_update(m3t_tex_best2s* b, float s, int index) {
+  if (s >= b->s1) return;
+  const float distance = sqrtf(s);
+  if (distance != distance) return;
+  if (b->b.d0 != b->b.d0 || distance < b->b.d0) {
+    b->b.d1 = b->b.d0;
+    b->s1 = b->s0;
+    b->b.d0 = distance;
+    b->s0 = s;
+    b->b.i0 = index;
+  } else if (b->b.d1 != b->b.d1 || distance < b->b.d1) {
+    b->b.d1 = distance;
+    b->s1 = s;
+  }
+}
+// `later` holds the best two of train descriptors that all follow those of `b`: its best is a candidate, then its
+// second (which can at most become the second here, so its index is never needed)
+M3T_TEX_FN void m3t_tex_best2f_append(m3t_tex_best2f* b, const m3t_tex_best2f* later) {
+  m3t_tex_best2f_update(b, later->d0, later->i0);
+  m3t_tex_best2f_update(b, later->d1, -1);
+}
+// :364-367 for an L2 match: two matches and NOT d0 / d1 >= threshold (0 / 0 and inf / inf = NaN: kept)
+M3T_TEX_FN bool m3t_tex_ratio_keeps_l2(const m3t_tex_best2f* b, float threshold) {
+  if (b->d1 != b->d1) return false;  // knn_match.size() < 2
+  return !(b->d0 / b->d1 >= threshold);
 }
 
 // What one data point subtracts from gradient_ (out[0 .. 6)) and from the lower triangle of hessian_ (out[6 .. 27),

@@ -572,14 +572,25 @@ class DepthModality(_Modality):
 class TextureModality(_Modality):
     """TextureModality behind its feature detector (texture_modality.cpp): the caller detects and describes features in
     the focused image of RegionOfInterest() and hands them over with SetFocusedFeatures (or SetFeatures, in full-image
-    coordinates); keyframes, matching, g/H and keyframe renewal run on the device."""
+    coordinates); keyframes, matching, g/H and keyframe renewal run on the device.
+    descriptor_norm="hamming": rows of descriptor_bytes (32 or 64) uint8, matched with the Hamming norm (ORB, BRISK,
+    FREAK).  descriptor_norm="l2": rows of descriptor_bytes / 4 float32, matched with the L2 norm as include/m3t_hip.h
+    pins it (SIFT: descriptor_bytes=512; DAISY: 4 * its number of floats); the built-in detector is refused there."""
 
-    def __init__(self, api, body, color_camera, silhouette_renderer, depth_camera=None, params=None, **kw):
+    def __init__(self, api, body, color_camera, silhouette_renderer, depth_camera=None, params=None,
+                 descriptor_norm="hamming", **kw):
+        if descriptor_norm not in ("hamming", "l2"):
+            raise ValueError("descriptor_norm=%r: \"hamming\" or \"l2\"" % (descriptor_norm,))
         self.api = api
         self.params = params if params is not None else TextureModalityParams(**kw)
+        self.descriptor_norm = descriptor_norm
         self.detector = None  # TextureDetectorParams while the built-in detector is set
-        self.id = api.call("texture_modality_create", C.byref(self.params), body.id, color_camera.id,
-                           silhouette_renderer.id, depth_camera.id if depth_camera is not None else -1)
+        self.id = api.call("texture_modality_create_l2" if descriptor_norm == "l2" else "texture_modality_create",
+                           C.byref(self.params), body.id, color_camera.id, silhouette_renderer.id,
+                           depth_camera.id if depth_camera is not None else -1)
+        # a row of descriptors as the caller hands it over and gets it back
+        self.descriptor_dtype = np.float32 if descriptor_norm == "l2" else np.uint8
+        self.descriptor_width = self.params.descriptor_bytes // 4 if descriptor_norm == "l2" else self.params.descriptor_bytes
 
     def ModelOcclusions(self, depth_renderer):
         self.api.call("texture_modality_model_occlusions", self.id, depth_renderer.id)
@@ -594,14 +605,28 @@ class TextureModality(_Modality):
         return ((int(roi[0]), int(roi[1]), int(roi[2]), int(roi[3])), np.float32(scale[0])) if valid.value else None
 
     def SetFeatures(self, keypoints, descriptors):
-        """keypoints: n x 2 in full-image coordinates; descriptors: n rows of descriptor_bytes"""
+        """keypoints: n x 2 in full-image coordinates; descriptors: n rows of descriptor_bytes (uint8), for an L2
+        modality an n x descriptor_bytes / 4 float32 array (another dtype or width: ValueError)"""
         keypoints = np.ascontiguousarray(keypoints, np.float32).reshape(-1, 2)
-        descriptors = np.ascontiguousarray(descriptors, np.uint8).reshape(len(keypoints), self.params.descriptor_bytes) \
-            if len(keypoints) == 0 else np.ascontiguousarray(descriptors, np.uint8).reshape(len(keypoints), -1)
-        if len(keypoints) and descriptors.shape[1] != self.params.descriptor_bytes:
-            raise ValueError("descriptors must have %d bytes per row" % self.params.descriptor_bytes)
+        if self.descriptor_norm == "l2":
+            descriptors = self._l2_rows(descriptors, len(keypoints))
+        else:
+            descriptors = np.ascontiguousarray(descriptors, np.uint8).reshape(len(keypoints), self.params.descriptor_bytes) \
+                if len(keypoints) == 0 else np.ascontiguousarray(descriptors, np.uint8).reshape(len(keypoints), -1)
+            if len(keypoints) and descriptors.shape[1] != self.params.descriptor_bytes:
+                raise ValueError("descriptors must have %d bytes per row" % self.params.descriptor_bytes)
         self.api.call("texture_modality_set_features", self.id, fptr(keypoints),
                       descriptors.ctypes.data_as(C.POINTER(C.c_uint8)), len(keypoints))
+
+    def _l2_rows(self, descriptors, n):
+        descriptors = np.asarray(descriptors)
+        if n == 0 and descriptors.size == 0:
+            return np.zeros((0, self.descriptor_width), np.float32)
+        if descriptors.dtype != np.float32:
+            raise ValueError("descriptors of an L2 modality must be float32, not %s" % descriptors.dtype)
+        if descriptors.ndim != 2 or descriptors.shape != (n, self.descriptor_width):
+            raise ValueError("descriptors must be %d x %d float32, not %s" % (n, self.descriptor_width, descriptors.shape))
+        return np.ascontiguousarray(descriptors)
 
     def SetDetector(self, params=None, builtin=True, **kw):
         """the built-in detector (TextureDetectorParams or its fields as keywords): detection is then enqueued with
@@ -611,19 +636,20 @@ class TextureModality(_Modality):
             self.detector = None
             self.api.call("texture_modality_set_detector", self.id, None)
             return
-        self.detector = params if params is not None else TextureDetectorParams(**kw)
-        self.api.call("texture_modality_set_detector", self.id, C.byref(self.detector))
+        detector = params if params is not None else TextureDetectorParams(**kw)
+        self.api.call("texture_modality_set_detector", self.id, C.byref(detector))  # (refused for an L2 modality)
+        self.detector = detector
 
     def features(self):
-        """(keypoints n x 2 in full-image coordinates, descriptors n x descriptor_bytes) the modality holds; waits for
-        the stream"""
+        """(keypoints n x 2 in full-image coordinates, descriptors n x descriptor_bytes uint8 -- for an L2 modality
+        n x descriptor_bytes / 4 float32) the modality holds; waits for the stream"""
         n = C.c_int()
         self.api.call("texture_modality_get_features", self.id, None, None, 0, C.byref(n))
         keypoints = np.zeros((max(n.value, 1), 2), np.float32)
         descriptors = np.zeros((max(n.value, 1), self.params.descriptor_bytes), np.uint8)
         self.api.call("texture_modality_get_features", self.id, fptr(keypoints),
                       descriptors.ctypes.data_as(C.POINTER(C.c_uint8)), n.value, C.byref(n))
-        return keypoints[:n.value], descriptors[:n.value]
+        return keypoints[:n.value], descriptors[:n.value].view(self.descriptor_dtype)
 
     def focused_image(self):
         """the grey focused image (height x width, uint8) of the last built-in detection, or None when it had no valid

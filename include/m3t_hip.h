@@ -247,8 +247,27 @@ int m3t_hip_depth_modality_use_silhouette_checking(m3t_hip_context*, int modalit
  * behind them runs on the device: keyframe reconstruction through the focused silhouette renderer with the two
  * occlusion tests (ComputeKeyframeData :933-1127), the brute-force 2-nearest-neighbour Hamming match with the ratio test
  * and the projection (CalculateCorrespondences :324-387), the Tukey-weighted g/H (:397-444, sums in the reference's
- * sequential order) and the keyframe renewal (CalculateResults :456-472, decided on the device).  Only Hamming-norm
- * descriptors: ORB (32 bytes), BRISK and FREAK (64 bytes).
+ * sequential order) and the keyframe renewal (CalculateResults :456-472, decided on the device).  Hamming-norm
+ * descriptors through texture_modality_create: ORB (32 bytes), BRISK and FREAK (64 bytes); L2-norm descriptors (SIFT,
+ * DAISY: cv::BFMatcher(cv::NORM_L2), :794-796) through texture_modality_create_l2.
+ * texture_modality_create_l2: the arguments and checks of texture_modality_create, for descriptors of D floats:
+ *   descriptor_bytes is 4 * D, a multiple of 16 in [16, 1024] (SIFT: 512; DAISY with OpenCV's defaults,
+ *   (3 * 8 + 1) * 8 = 200 floats: 800), anything else M3T_ERR_INVALID_ARGUMENT.  Rows of descriptor_bytes in
+ *   set_features / get_features are then D floats in host byte order.  The norm, which is the contract: s = 0, then
+ *   s = s + (q[k] - t[k]) * (q[k] - t[k]) for k = 0 .. D - 1 in ascending order, every operation rounded to f32 and
+ *   none contracted; the distance is sqrtf(s), correctly rounded.  That is std::sqrt(normL2Sqr()) of OpenCV's
+ *   batchDistL2_32f with the order of the sum fixed (OpenCV's own depends on its SIMD build).  OpenCV's SIFT
+ *   descriptors hold integers 0 .. 255 as floats: every square and every partial sum is then an integer of at most
+ *   128 * 255^2 = 8 323 200 < 2^24, exact in f32 in every order, so the rule gives the bits of any OpenCV build there.
+ *   This is an argument, not a measurement: no OpenCV was at hand to compare with.  Descriptors that are not
+ *   integer-valued (DAISY) are held to the rule alone.  The best two are compared by their distances (the sqrtf
+ *   values, not the sums: two different sums can round to one distance, and the lower index then ranks first); a NaN
+ *   distance satisfies no `<` and never enters; +inf is a distance like any other; the ratio test is d0 / d1 in f32.
+ *   The match runs tiled over keyframes and queries (m3t_texture_l2.hip), the Hamming match one workgroup a modality.
+ *   Device memory per modality: the keyframe ring of n_keyframes x 4096 x D floats (26 MB at D = 200 and 8 keyframes)
+ *   and 12 bytes of best-two scratch per ring entry.  set_detector stays M3T_ERR_UNSUPPORTED on such a modality (the
+ *   built-in detector writes 32-byte binary descriptors), and what is refused for a caller-fed modality stays refused.
+ *   Hamming and L2 modalities may share a context.
  * texture_modality_create: the renderer has to be a focused SILHOUETTE renderer with id_type BODY that references the
  *   body (refused otherwise: the reference only warns, :59-63, and then matches nothing); depth_camera_id = -1 unless
  *   measure_occlusions.  The body needs its geometry (body_set_geometry: the region of interest uses its diameter).
@@ -291,6 +310,8 @@ int m3t_hip_depth_modality_use_silhouette_checking(m3t_hip_context*, int modalit
  * communicator or reduce callback, are M3T_ERR_UNSUPPORTED in such a context. */
 int m3t_hip_texture_modality_create(m3t_hip_context*, const m3t_texture_modality_params*, int body_id, int color_camera_id,
                                     int silhouette_renderer_id, int depth_camera_id);
+int m3t_hip_texture_modality_create_l2(m3t_hip_context*, const m3t_texture_modality_params*, int body_id,
+                                       int color_camera_id, int silhouette_renderer_id, int depth_camera_id);
 int m3t_hip_texture_modality_model_occlusions(m3t_hip_context*, int modality_id, int depth_renderer_id);
 int m3t_hip_texture_modality_get_region_of_interest(m3t_hip_context*, int modality_id, int roi[4], float* scale,
                                                     int* valid);

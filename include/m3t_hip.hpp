@@ -334,6 +334,20 @@ class TextureModality : public Modality {
                                                     silhouette_renderer.id(), depth_camera ? depth_camera->id() : -1),
                     "TextureModality");
   }
+  // L2-norm descriptors (SIFT, DAISY): params.descriptor_bytes is 4 * the floats of a descriptor, rows of SetFeatures
+  // and features() are those floats (m3t_hip_texture_modality_create_l2)
+  struct L2Norm {};
+  TextureModality(ContextPtr c, L2Norm, const Body& body, const ColorCamera& color_camera,
+                  const FocusedSilhouetteRenderer& silhouette_renderer, const m3t_texture_modality_params& params,
+                  const DepthCamera* depth_camera = nullptr) {
+    c_ = std::move(c);
+    id_ = c_->Check(m3t_hip_texture_modality_create_l2(c_->get(), &params, body.id(), color_camera.id(),
+                                                       silhouette_renderer.id(), depth_camera ? depth_camera->id() : -1),
+                    "TextureModality");
+  }
+  bool SetFeaturesL2(const float* keypoints_xy, const float* descriptors, int n) {
+    return SetFeatures(keypoints_xy, reinterpret_cast<const uint8_t*>(descriptors), n);
+  }
   bool ModelOcclusions(const FocusedBasicDepthRenderer& renderer) {
     return c_->Step(m3t_hip_texture_modality_model_occlusions(c_->get(), id_, renderer.id()));
   }

@@ -137,10 +137,10 @@ typedef struct m3t_depth_modality_params {
 } m3t_depth_modality_params;
 
 /* TextureModality behind its feature detector (texture_modality.h:400-407, 431-436).  Detection stays with the caller
- * (the reference delegates it to one of five OpenCV classes); descriptors are Hamming-norm bit strings: ORB 32 bytes,
- * BRISK and FREAK 64 bytes. */
+ * (the reference delegates it to one of five OpenCV classes); descriptors are Hamming-norm bit strings (ORB 32 bytes,
+ * BRISK and FREAK 64 bytes) or, through m3t_hip_texture_modality_create_l2, L2-norm rows of floats (SIFT, DAISY). */
 typedef struct m3t_texture_modality_params {
-  int descriptor_bytes; /* 32 or 64 */
+  int descriptor_bytes; /* 32 or 64; create_l2: 4 * the floats of a descriptor, a multiple of 16 in [16, 1024] */
   int focused_image_size;
   float descriptor_distance_threshold;
   float tukey_norm_constant;
