@@ -22,6 +22,7 @@
 
 #include "../../include/m3t_hip.h"
 #include "m3t_device.h"
+#include "m3t_host_resources.h"
 #include "m3t_view_rows.h"
 #include "m3t_step_plan.h"
 #include "m3t_render_plan.h"
@@ -56,64 +57,17 @@ namespace {
 
 thread_local std::string g_create_error;
 
-struct DevMem {
-  void* p = nullptr;
-  size_t bytes = 0;
-  DevMem() = default;
-  DevMem(const DevMem&) = delete;
-  DevMem& operator=(const DevMem&) = delete;
-  ~DevMem() { release(); }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    bytes = 0;
-  }
-  hipError_t alloc(size_t n) {
-    release();
-    if (n == 0) n = 16;
-    hipError_t e = hipMalloc(&p, n);
-    if (e == hipSuccess) bytes = n;
-    return e;
-  }
-  template <typename T>
-  T* as() const { return static_cast<T*>(p); }
-};
-
-// Blocks of mapped host memory taken in turn by enqueued calls: a call fills its block, its launches read it in place, and
-// the call kDepth calls later waits for them before it takes the block again.
-struct MappedRing {
-  static constexpr int kDepth = 4;
-  void* block[kDepth] = {nullptr};
-  size_t bytes[kDepth] = {0};
-  hipEvent_t done[kDepth] = {nullptr};
-  int next = 0;
-  MappedRing() = default;
-  MappedRing(const MappedRing&) = delete;
-  MappedRing& operator=(const MappedRing&) = delete;
-  ~MappedRing() {
-    for (int i = 0; i < kDepth; ++i) {
-      if (block[i]) (void)hipHostFree(block[i]);
-      if (done[i]) (void)hipEventDestroy(done[i]);
-    }
-  }
-  hipError_t Acquire(size_t n, void** host, void** dev, int* slot) {
-    const int s = *slot = next;
-    next = (s + 1) % kDepth;
-    hipError_t e = hipSuccess;
-    if (!done[s] && (e = hipEventCreateWithFlags(&done[s], hipEventDisableTiming)) != hipSuccess) return e;
-    if ((e = hipEventSynchronize(done[s])) != hipSuccess) return e;  // the call kDepth calls ago: normally long complete
-    if (bytes[s] < n) {
-      if (block[s] && (e = hipHostFree(block[s])) != hipSuccess) return e;
-      block[s] = nullptr;
-      bytes[s] = 0;
-      if ((e = hipHostMalloc(&block[s], n * 2, hipHostMallocMapped)) != hipSuccess) return e;
-      bytes[s] = n * 2;
-    }
-    *host = block[s];
-    return hipHostGetDevicePointer(dev, block[s], 0);
-  }
-  hipError_t Release(int slot, hipStream_t stream) { return hipEventRecord(done[slot], stream); }
-};
+using m3t_res::CreateMaskedStream;
+using m3t_res::DevMem;
+using m3t_res::Event;
+using m3t_res::EventPair;
+using m3t_res::HostBlock;
+using m3t_res::kMapped;
+using m3t_res::kPinned;
+using m3t_res::Stream;
+using m3t_res::UploadTable;
+// m3t_hip_reset_* / m3t_hip_judge_* / set_features: a call's arguments in mapped blocks, read in place by its launches
+using MappedRing = m3t_res::HostRing<4, kMapped>;
 
 struct Model {
   bool region = true;
@@ -138,7 +92,7 @@ struct Camera {
   std::vector<bool> has_image;
   std::vector<long> last_read_step;  // per slot: the last streaming step that read it (-1: none)
   std::vector<bool> slot_is_roi;     // per slot: only the trackers' rectangle of the frame was uploaded (m3t_ingest.hip)
-  std::vector<hipEvent_t> slot_copied;  // per slot: behind its last camera_upload_slot_async (m3t_hip_camera_slot_sync); lazily made
+  std::vector<Event> slot_copied;  // per slot: behind its last camera_upload_slot_async (m3t_hip_camera_slot_sync); lazily made
   DevMem ring;          // this camera's own frame ring, or empty when it lives in a shared slab
   int slab = -1, slab_index = 0;  // shared slab (m3t_hip_cameras_set_ring): [slot][camera of the group][frame]
   uint8_t* frames = nullptr;      // slot 0 of this camera
@@ -157,44 +111,28 @@ struct FrameSlab {  // the frame rings of a group of cameras of equal geometry i
   std::vector<int> cameras;
   // per ring slot: behind the last batch upload / rectangle pull into it (m3t_hip_camera_slot_sync of any of its
   // cameras).  ONE event per batch-frame: an event per camera cost a 64-camera upload 0.3 ms of host time.
-  std::vector<hipEvent_t> slot_copied;
-  ~FrameSlab() {
-    for (auto& e : slot_copied)
-      if (e) (void)hipEventDestroy(e);
-  }
+  std::vector<Event> slot_copied;
 };
-
-// A stream of the context.  With CUs reserved for ingest (m3t_hip_reserve_ingest_cus) the compute stream runs on the
-// CUs of mask bits [0, CUs - n) and copy stream 0 -- the one the ROI pull kernel is launched on -- on bits
-// [CUs - n, CUs).  Bit i of a mask belongs to XCD i mod 8 (amdkfd deals the bits round-robin; tools/ubench_cumask.hip
-// counts 30 / 2 CUs per XCD for 240 / 16 bits), inside an XCD the highest bits are the last CU of each shader engine.
-hipError_t CreateMaskedStream(int ingest_cus, int cus, hipStream_t* stream, bool ingest_side) {
-  if (ingest_cus <= 0) return hipStreamCreateWithFlags(stream, hipStreamNonBlocking);
-  const int split = cus - ingest_cus;
-  std::vector<uint32_t> mask(size_t(cus + 31) / 32, 0u);
-  for (int i = ingest_side ? split : 0; i < (ingest_side ? cus : split); ++i) mask[size_t(i) / 32] |= 1u << (i % 32);
-  return hipExtStreamCreateWithCUMask(stream, uint32_t(mask.size()), mask.data());
-}
 
 // Asynchronous ingest: frame copies run on streams of their own beside the tracking kernels.  The ledger decides
 // (m3t_ingest_plan.h), the methods carry its decisions out; DESIGN.md section 1 ("Frame ingest") states the protocol.
 struct Ingest {
   static constexpr int kCopyStreams = m3t_ingest::kCopyStreams;
-  hipStream_t copy_stream[kCopyStreams] = {nullptr};
-  hipEvent_t copies_done[kCopyStreams] = {nullptr}, step_done[m3t_ingest::kStepEvents] = {nullptr};
+  Stream copy_stream[kCopyStreams];
+  Event copies_done[kCopyStreams], step_done[m3t_ingest::kStepEvents];
   m3t_ingest::Ledger ledger;
   std::vector<void*> registered;  // Register
   bool async() const { return ledger.async; }
   bool untracked() const { return ledger.untracked; }
   void LaunchedUntracked() { ledger.LaunchedUntracked(); }
-  hipStream_t Stream(int cs) const { return copy_stream[cs]; }
+  hipStream_t CopyStream(int cs) const { return copy_stream[cs].get(); }
   hipError_t Keep(const m3t_ingest::Ledger& before, hipError_t e) {  // a runtime call that fails leaves the ledger as it was
     if (e != hipSuccess) ledger = before;
     return e;
   }
-  static hipError_t CreateStreams(int ingest_cus, int cus, hipStream_t (&streams)[kCopyStreams]) {
+  static hipError_t CreateStreams(int ingest_cus, int cus, Stream (&streams)[kCopyStreams]) {
     hipError_t e = CreateMaskedStream(ingest_cus, cus, &streams[0], true);
-    for (int i = 1; i < kCopyStreams && e == hipSuccess; ++i) e = hipStreamCreateWithFlags(&streams[i], hipStreamNonBlocking);
+    for (int i = 1; i < kCopyStreams && e == hipSuccess; ++i) e = streams[i].Create(hipStreamNonBlocking);
     return e;
   }
   hipError_t EnsureStarted(int ingest_cus, int cus) {
@@ -202,16 +140,16 @@ struct Ingest {
     if (!ledger.Start()) return hipSuccess;
     hipError_t e = CreateStreams(ingest_cus, cus, copy_stream);
     for (auto& ev : copies_done)
-      if (e == hipSuccess) e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+      if (e == hipSuccess) e = ev.Ensure(hipEventDisableTiming);
     for (auto& ev : step_done)
-      if (e == hipSuccess) e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+      if (e == hipSuccess) e = ev.Ensure(hipEventDisableTiming);
     return Keep(before, e);
   }
   // what a decision of the ledger asks for; cs: the copy stream that waits for a step event (-1: the host does)
   hipError_t Obey(const m3t_ingest::Wait& w, int cs, hipStream_t compute) const {
     if (w.kind == m3t_ingest::Wait::kComputeStream) return hipStreamSynchronize(compute);
     if (w.kind == m3t_ingest::Wait::kNothing) return hipSuccess;
-    return cs < 0 ? hipEventSynchronize(step_done[w.event]) : hipStreamWaitEvent(copy_stream[cs], step_done[w.event], 0);
+    return cs < 0 ? hipEventSynchronize(step_done[w.event].get()) : hipStreamWaitEvent(copy_stream[cs].get(), step_done[w.event].get(), 0);
   }
   // a copy on copy stream cs overwrites a slot only behind the launches that read it last (step last_read) ...
   hipError_t OrderCopy(int cs, long last_read, hipStream_t compute) {
@@ -221,11 +159,11 @@ struct Ingest {
   // ... and the host waits for those launches
   hipError_t WaitForReader(long last_read, hipStream_t compute) const { return Obey(ledger.WaitForReader(last_read), -1, compute); }
   // the "slot copied" event of a camera or a slab (made on first use) behind what copy stream cs holds for the slot
-  hipError_t SlotCopied(std::vector<hipEvent_t>* events, int n_slots, int slot, int cs) {
-    if (events->size() < size_t(n_slots)) events->resize(size_t(n_slots), nullptr);
-    hipEvent_t& copied = (*events)[slot];
-    hipError_t e = copied ? hipSuccess : hipEventCreateWithFlags(&copied, hipEventDisableTiming);
-    if (e == hipSuccess && (e = hipEventRecord(copied, copy_stream[cs])) == hipSuccess) ledger.CopyEnqueued(cs);
+  hipError_t SlotCopied(std::vector<Event>* events, int n_slots, int slot, int cs) {
+    if (events->size() < size_t(n_slots)) events->resize(size_t(n_slots));
+    Event& copied = (*events)[slot];
+    hipError_t e = copied.Ensure(hipEventDisableTiming);
+    if (e == hipSuccess && (e = hipEventRecord(copied.get(), copy_stream[cs].get())) == hipSuccess) ledger.CopyEnqueued(cs);
     return e;
   }
   // frames enqueued on the copy streams so far become visible to everything launched on `compute` from here on
@@ -233,8 +171,8 @@ struct Ingest {
     const m3t_ingest::Ledger before = ledger;
     hipError_t e = hipSuccess;
     for (unsigned k = 0, pending = ledger.TakePending(); k < kCopyStreams && e == hipSuccess; ++k)
-      if ((pending >> k & 1u) && (e = hipEventRecord(copies_done[k], copy_stream[k])) == hipSuccess)
-        e = hipStreamWaitEvent(compute, copies_done[k], 0);
+      if ((pending >> k & 1u) && (e = hipEventRecord(copies_done[k].get(), copy_stream[k].get())) == hipSuccess)
+        e = hipStreamWaitEvent(compute, copies_done[k].get(), 0);
     return Keep(before, e);
   }
   // Launches on `compute` read the current frames of the cameras listed (ids null: of all of them): a later asynchronous
@@ -243,7 +181,7 @@ struct Ingest {
     const m3t_ingest::Ledger before = ledger;
     const m3t_ingest::ReadMark mark = ledger.MarkRead();
     if (mark.event < 0) return hipSuccess;
-    const hipError_t e = Keep(before, hipEventRecord(step_done[mark.event], compute));
+    const hipError_t e = Keep(before, hipEventRecord(step_done[mark.event].get(), compute));
     for (size_t i = 0; e == hipSuccess && i < (ids ? ids->size() : cameras.size()); ++i) {
       Camera& c = *cameras[ids ? size_t((*ids)[i]) : i];
       c.last_read_step[c.current] = mark.step;
@@ -253,7 +191,7 @@ struct Ingest {
   hipError_t SyncCopies() const {
     hipError_t e = hipSuccess;
     for (auto& cs : copy_stream)
-      if (cs && e == hipSuccess) e = hipStreamSynchronize(cs);
+      if (cs && e == hipSuccess) e = hipStreamSynchronize(cs.get());
     return e;
   }
   hipError_t Register(void* ptr, size_t bytes) {
@@ -267,24 +205,13 @@ struct Ingest {
     if (e == hipSuccess && (e = hipHostUnregister(ptr)) == hipSuccess) registered.erase(std::find(registered.begin(), registered.end(), ptr));
     return e;
   }
-  void ReplaceStreams(const hipStream_t (&streams)[kCopyStreams]) {  // (synchronised by the caller: nothing is pending)
-    for (int i = 0; i < kCopyStreams; ++i) {
-      if (copy_stream[i]) (void)hipStreamDestroy(copy_stream[i]);
-      copy_stream[i] = streams[i];
-    }
+  void ReplaceStreams(Stream (&streams)[kCopyStreams]) {  // (synchronised by the caller: nothing is pending)
+    for (int i = 0; i < kCopyStreams; ++i) copy_stream[i] = std::move(streams[i]);
     (void)ledger.TakePending();
   }
-  void Shutdown() {  // m3t_hip_destroy
-    for (auto& cs : copy_stream) {
-      if (!cs) continue;
-      (void)hipStreamSynchronize(cs);
-      (void)hipStreamDestroy(cs);
-    }
+  void UnregisterAll() {  // m3t_hip_destroy, behind SyncCopies
     for (void* p : registered) (void)hipHostUnregister(p);
-    for (auto& e : copies_done)
-      if (e) (void)hipEventDestroy(e);
-    for (auto& e : step_done)
-      if (e) (void)hipEventDestroy(e);
+    registered.clear();
   }
 };
 
@@ -389,9 +316,8 @@ struct Judge {  // m3t_hip_judge_*: the evaluators' judgement of a list of bodie
   DevMem d_add_bodies, d_add_parts, d_add_partial;
   int n_add_bodies = 0, n_add_parts = 0;
   bool any_add_split = false;
-  m3t_body_judgement* rows_host = nullptr;  // [n_rows_max][n_bodies], written by the kernels in place
-  m3t_body_judgement* rows_dev = nullptr;
-  std::vector<hipEvent_t> row_done;         // per row: behind the launches of its call
+  HostBlock rows;               // mapped: [n_rows_max][n_bodies], written by the kernels in place
+  std::vector<Event> row_done;  // per row: behind the launches of its call; made on first use
   MappedRing args;  // the ground-truth poses and the region-modality lists of a call, read in place by its launches
   // m3t_hip_judge_set_structures: the structures' groups of listed bodies and a second table of rows
   int n_structures = 0;
@@ -401,21 +327,15 @@ struct Judge {  // m3t_hip_judge_*: the evaluators' judgement of a list of bodie
   // m3t_hip_judge_set_reset_renderers: a resetting call may run start-modality renderers, decided on the device
   std::vector<int> targets;
   bool reset_renderers = false;
-  m3t_structure_judgement* structure_rows_host = nullptr;  // [n_rows_max][n_structures], written by the kernel in place
-  m3t_structure_judgement* structure_rows_dev = nullptr;
-  ~Judge() {
-    if (rows_host) (void)hipHostFree(rows_host);
-    if (structure_rows_host) (void)hipHostFree(structure_rows_host);
-    for (auto& e : row_done)
-      if (e) (void)hipEventDestroy(e);
-  }
+  HostBlock structure_rows;  // mapped: [n_rows_max][n_structures], written by the kernel in place
 };
 
 }  // namespace
 
 struct m3t_hip_context {
   int device = 0;
-  hipStream_t stream = nullptr;
+  Stream compute;  // declared before every event and block used on it: destroyed behind them (m3t_hip_destroy)
+  hipStream_t stream = nullptr;  // compute.get(), as the launches take it
   hipDeviceProp_t prop{};
   std::string error;
   std::vector<std::unique_ptr<Model>> region_models, depth_models;
@@ -503,8 +423,7 @@ struct m3t_hip_context {
   size_t split_objects = 0;  // capacity of d_split
   unsigned split_seq = 0;    // launch counter inside the granule tags
   int split_parts_override = 0;  // m3t_hip_set_object_split(ctx, n > 1): workgroups per object (0: automatic)
-  unsigned* split_abort_host = nullptr;  // mapped host word: sequence number of a split step that gave up
-  unsigned* split_abort_dev = nullptr;   // the same word as the device sees it
+  HostBlock split_abort;  // mapped host word: sequence number of a split step that gave up (MappedWord)
   unsigned split_abort_seen = 0;
   unsigned split_launches = 0;  // never reset (unlike split_seq): the value an aborting launch leaves in the host word
   int last_step_shape[4] = {0, 0, 0, 0};  // m3t_hip_get_step_shape
@@ -515,8 +434,7 @@ struct m3t_hip_context {
   size_t lds_compact = 0;
   CompactLayout compact_table{};  // ... with the pair table compacted in LDS (tracking_step_compact_table_kernel)
   size_t lds_compact_table = 0;   // 0: not available for this context's modalities
-  unsigned* table_overflow_host = nullptr;  // mapped: mixed bins that did not fit the LDS table, largest over the workgroups
-  unsigned* table_overflow_dev = nullptr;
+  HostBlock table_overflow;  // mapped word: mixed bins that did not fit the LDS table, largest over the workgroups
   bool compact_possible = false;       // every modality fits the kernel's assumptions (UploadTables)
   bool compact_fuses_histogram = false;  // ... and the count table fits next to the scratch block (<= 16 bins)
   // what the last step launched (m3t_step_plan.h): m3t_hip_get_step_variant reports it, m3t_hip_get_step_kernel too
@@ -555,35 +473,32 @@ struct m3t_hip_context {
   // the previous step's end does not vouch for them (first step, poses set by the host, other launches in between).
   // A rectangle upload reads the newest one and, for adaptive margins, the one before it.
   static constexpr int kRoiSnapshots = 3;
-  hipEvent_t roi_snapshot_done[kRoiSnapshots] = {nullptr, nullptr, nullptr};
+  Event roi_snapshot_done[kRoiSnapshots];
   bool roi_snapshot_valid = false;
   int roi_use = 0;              // the snapshot the next rectangle upload reads: the poses at the start of the step enqueued last
   int roi_prev = -1;            // the snapshot one step before roi_use (-1: none)
   int roi_end_index = 0;        // where the last step's end-of-step snapshot went
   bool roi_end_valid = false;   // ... and whether it still describes the device poses
-  int* roi_miss_host = nullptr;             // mapped: [0] count, [1 ..] body ids: steps that left their rectangles (and were repeated)
-  int* roi_miss_dev = nullptr;
-  int* roi_unrecovered_host = nullptr;      // the same for bodies whose repeat missed again (no whole frame within reach)
-  int* roi_unrecovered_dev = nullptr;
+  // one mapped block of two lists, each [0] count, [1 ..] body ids: steps that left their rectangles (and were
+  // repeated), and behind them the bodies whose repeat missed again (no whole frame within reach)
   static constexpr int kRoiMissCapacity = 255;
+  HostBlock roi_miss;
+  static int* RoiMissList(void* block, bool unrecovered) {  // (block: roi_miss.host or .dev; null before ROI ingest)
+    return block ? static_cast<int*>(block) + (unrecovered ? kRoiMissCapacity + 1 : 0) : nullptr;
+  }
   int np_max = 0, off_points = 0;
   size_t lds_track = 0, lds_corr = 0, lds_hist = 0, lds_depth = 0;
   bool hist_counts_in_lds = true;
   // optional HIP-event timing of the two per-frame kernels (bench.py roofline leg)
   // pinned staging ring for the camera table: a frame switch is an async 1-2 KB copy, no host sync
-  static constexpr int kStage = 8;
-  void* cam_stage[kStage] = {nullptr};
-  size_t cam_stage_bytes = 0;
-  hipEvent_t cam_stage_done[kStage] = {nullptr};
-  int cam_stage_next = 0;
+  m3t_res::HostRing<8, kPinned> cam_staging;
   MappedRing reset_args;  // m3t_hip_reset_bodies / _structures: the call's lists and poses, read in place by its launches
   std::vector<std::unique_ptr<Judge>> judges;  // m3t_hip_judge_create
   Ingest ingest;  // asynchronous frame uploads and their order against the launches that read the frames
   bool timing = false;        // m3t_hip_set_kernel_timing(1): an event pair around every launch
   bool timing_region = false; // m3t_hip_set_kernel_timing(2): ONE pair around all launches until the query
-  hipEvent_t region_a = nullptr, region_b = nullptr;
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-  struct Pending { hipEvent_t a, b; int which; };
+  EventPair region;
+  struct Pending { EventPair events; int which; };
   std::vector<Pending> pending;
   double kernel_ms[2] = {0.0, 0.0};
   int kernel_launches[2] = {0, 0};
@@ -758,15 +673,12 @@ int CreateModel(Ctx* ctx, bool region, int n_views, int n_points, const float* p
       for (int k = 0; k < (region ? 8 : 6); ++k) p8[i * 8 + k] = pts[i * pf + k];
     for (int v = 0; v < n_views; ++v)
       for (int k = 0; k < 3; ++k) o4[size_t(v) * 4 + k] = ori[size_t(v) * 3 + k];
-    HIPCHK(m->points8.alloc(p8.size() * 4));
-    HIPCHK(m->orientations4.alloc(o4.size() * 4));
-    HIPCHK(hipMemcpy(m->points8.p, p8.data(), p8.size() * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(m->orientations4.p, o4.data(), o4.size() * 4, hipMemcpyHostToDevice));
+    HIPCHK(UploadTable(&m->points8, p8));
+    HIPCHK(UploadTable(&m->orientations4, o4));
   }
   if (n_views > M3T_VIEW_ROW) {
     const std::vector<float> rows = m3t_view_rows(ori, n_views);  // closest_view_local's table (m3t_view_rows.h)
-    HIPCHK(m->view_neighbors.alloc(rows.size() * 4));
-    HIPCHK(hipMemcpy(m->view_neighbors.p, rows.data(), rows.size() * 4, hipMemcpyHostToDevice));
+    HIPCHK(UploadTable(&m->view_neighbors, rows));
   }
   auto& vec = region ? ctx->region_models : ctx->depth_models;
   vec.push_back(std::move(m));
@@ -837,15 +749,9 @@ int ResidentBlocks(Ctx* ctx, K kernel, int threads, size_t lds) {
 }
 
 // A word the kernels write with system scope and the host reads in place: 64 zeroed bytes of mapped host memory,
-// allocated on first use and freed in m3t_hip_destroy.
-int MappedWord(Ctx* ctx, unsigned** host, unsigned** dev) {
-  if (*host) return M3T_OK;
-  void *h = nullptr, *d = nullptr;
-  HIPCHK(hipHostMalloc(&h, 64, hipHostMallocMapped));
-  std::memset(h, 0, 64);
-  HIPCHK(hipHostGetDevicePointer(&d, h, 0));
-  *host = static_cast<unsigned*>(h);
-  *dev = static_cast<unsigned*>(d);
+// allocated on first use.
+int MappedWord(Ctx* ctx, HostBlock* word) {
+  if (!word->host) HIPCHK(word->Alloc(64, kMapped, true));
   return M3T_OK;
 }
 
@@ -853,8 +759,8 @@ int MappedWord(Ctx* ctx, unsigned** host, unsigned** dev) {
 // are all resident by construction; the bounded wait exists so that a surprise cannot hang the device.)
 int CheckSplitExchange(Ctx* ctx) {
   // the word lives in mapped host memory: no copy, no synchronisation; the kernel writes it with system scope
-  if (!ctx->split_abort_host) return M3T_OK;
-  const unsigned value = __atomic_load_n(ctx->split_abort_host, __ATOMIC_ACQUIRE);
+  if (!ctx->split_abort.host) return M3T_OK;
+  const unsigned value = __atomic_load_n(ctx->split_abort.as<unsigned>(), __ATOMIC_ACQUIRE);
   if (value != ctx->split_abort_seen) {
     ctx->split_abort_seen = value;
     using m3t_step::StepKernel;
@@ -1128,11 +1034,10 @@ int UploadTreeTables(Ctx* ctx) {
     o.partial_offset = partial_total;
     partial_total += size_t(dof) * dof + dof;
   }
-  HIPCHK(ctx->d_links.alloc(std::max<size_t>(1, links.size()) * sizeof(LinkDev)));
-  HIPCHK(ctx->d_links_alt.alloc(std::max<size_t>(1, links.size()) * sizeof(LinkDev)));
-  HIPCHK(ctx->d_constraints.alloc(std::max<size_t>(1, cons.size()) * sizeof(ConstraintDev)));
-  HIPCHK(ctx->d_soft.alloc(std::max<size_t>(1, soft.size()) * sizeof(SoftConstraintDev)));
-  HIPCHK(ctx->d_treeopts.alloc(std::max<size_t>(1, opts.size()) * sizeof(TreeOptDev)));
+  HIPCHK(UploadTable(&ctx->d_links, links));
+  HIPCHK(UploadTable(&ctx->d_links_alt, links));
+  HIPCHK(UploadTable(&ctx->d_constraints, cons));
+  HIPCHK(UploadTable(&ctx->d_soft, soft));
   HIPCHK(ctx->d_work.alloc(std::max<size_t>(1, work_total) * 4));
   // the structures' work arrays live in LDS when the largest fits (one wave per structure, m3t_links.hip)
   ctx->tree_lds = tree_work_max * 4 <= size_t(152) * 1024 ? tree_work_max * 4 : 0;
@@ -1145,8 +1050,7 @@ int UploadTreeTables(Ctx* ctx) {
   {
     std::vector<int> first(std::max<size_t>(1, opts.size()), 0);
     for (size_t oi = 0; oi < opts.size(); ++oi) first[oi] = int(link_off[oi]);
-    HIPCHK(ctx->d_link_first.alloc(first.size() * sizeof(int)));
-    HIPCHK(hipMemcpy(ctx->d_link_first.p, first.data(), first.size() * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(UploadTable(&ctx->d_link_first, first));
     ctx->link_sums_count = links.size() * 42;
     HIPCHK(ctx->d_link_sums.alloc(std::max<size_t>(1, ctx->link_sums_count) * 4));
     HIPCHK(hipMemset(ctx->d_link_sums.p, 0, ctx->d_link_sums.bytes));
@@ -1174,12 +1078,6 @@ int UploadTreeTables(Ctx* ctx) {
     d.links_alt = ctx->d_links_alt.as<LinkDev>() + link_off[oi];
     d.first_link = int(link_off[oi]);
   }
-  if (!links.empty()) {
-    HIPCHK(hipMemcpy(ctx->d_links.p, links.data(), links.size() * sizeof(LinkDev), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(ctx->d_links_alt.p, links.data(), links.size() * sizeof(LinkDev), hipMemcpyHostToDevice));
-  }
-  if (!cons.empty()) HIPCHK(hipMemcpy(ctx->d_constraints.p, cons.data(), cons.size() * sizeof(ConstraintDev), hipMemcpyHostToDevice));
-  if (!soft.empty()) HIPCHK(hipMemcpy(ctx->d_soft.p, soft.data(), soft.size() * sizeof(SoftConstraintDev), hipMemcpyHostToDevice));
   // tracking_step_tree_kernel: the links that carry modalities, one workgroup each (at most one region and one
   // depth modality per link, every modality on a link), their exchange buffers, the LDS of a structure's copy
   {
@@ -1236,13 +1134,11 @@ int UploadTreeTables(Ctx* ctx) {
       if (int(o.order.size()) > M3T_TREE_FUSED_MAX_LINKS || o.dof + o.n_rows > M3T_TREE_FUSED_MAX_SIZE) possible = false;
       if (!o.constraints.empty() || !o.soft_constraints.empty()) ctx->tree_constrained = true;
     }
-    HIPCHK(ctx->d_treesteps.alloc(std::max<size_t>(1, steps.size()) * sizeof(TreeStepDev)));
-    HIPCHK(ctx->d_tracked_links.alloc(std::max<size_t>(1, tracked.size()) * sizeof(int)));
+    HIPCHK(UploadTable(&ctx->d_treesteps, steps));
+    HIPCHK(UploadTable(&ctx->d_tracked_links, tracked));
     HIPCHK(ctx->d_tree_exchange.alloc(std::max<size_t>(1, exchange_total) * 8));
     HIPCHK(hipMemset(ctx->d_tree_exchange.p, 0, ctx->d_tree_exchange.bytes));
     ctx->tree_seq = 0;
-    if (!steps.empty()) HIPCHK(hipMemcpy(ctx->d_treesteps.p, steps.data(), steps.size() * sizeof(TreeStepDev), hipMemcpyHostToDevice));
-    if (!tracked.empty()) HIPCHK(hipMemcpy(ctx->d_tracked_links.p, tracked.data(), tracked.size() * sizeof(int), hipMemcpyHostToDevice));
     for (size_t oi = 0; oi < opts.size(); ++oi) {
       opts[oi].tracked_links = ctx->d_tracked_links.as<int>() + tracked_off[oi];
       opts[oi].exchange = ctx->d_tree_exchange.as<unsigned long long>() + exchange_off[oi];
@@ -1250,7 +1146,7 @@ int UploadTreeTables(Ctx* ctx) {
     ctx->n_treesteps = int(steps.size());
     ctx->tree_fused_possible = possible;
   }
-  if (!opts.empty()) HIPCHK(hipMemcpy(ctx->d_treeopts.p, opts.data(), opts.size() * sizeof(TreeOptDev), hipMemcpyHostToDevice));
+  HIPCHK(UploadTable(&ctx->d_treeopts, opts));  // (last: its entries point into the tables above)
   return M3T_OK;
 }
 
@@ -1294,9 +1190,7 @@ int UploadRendererTables(Ctx* ctx) {
       sh[i].histogram_norm = h.hist_norm.as<float2>();
       sh[i].counts = h.counts.as<unsigned long long>();
     }
-    HIPCHK(ctx->d_shared_histograms.alloc(std::max<size_t>(1, sh.size()) * sizeof(SharedHistogramsDev)));
-    if (!sh.empty())
-      HIPCHK(hipMemcpy(ctx->d_shared_histograms.p, sh.data(), sh.size() * sizeof(SharedHistogramsDev), hipMemcpyHostToDevice));
+    HIPCHK(UploadTable(&ctx->d_shared_histograms, sh));
   }
   const size_t n = ctx->renderers.size();
   std::vector<RendererDev> table(n);
@@ -1344,8 +1238,7 @@ int UploadRendererTables(Ctx* ctx) {
     d.n_survivors = h.n_survivors.as<int>();
     d.survivor_capacity = h.survivor_capacity;
   }
-  HIPCHK(ctx->d_renderers.alloc(std::max<size_t>(1, n) * sizeof(RendererDev)));
-  if (n) HIPCHK(hipMemcpy(ctx->d_renderers.p, table.data(), n * sizeof(RendererDev), hipMemcpyHostToDevice));
+  HIPCHK(UploadTable(&ctx->d_renderers, table));
   auto slot_of = [&](int renderer, int body) {
     const std::vector<int>& ref = ctx->renderers[renderer]->referenced;
     for (size_t k = 0; k < ref.size(); ++k)
@@ -1389,20 +1282,12 @@ int UploadRendererTables(Ctx* ctx) {
   const std::vector<int> pairs_region = RendererPairs(ctx, list_region), pairs_all = RendererPairs(ctx, list_all);
   ctx->n_render_region_pairs = int(pairs_region.size() / 2);
   ctx->n_render_all_pairs = int(pairs_all.size() / 2);
-  HIPCHK(ctx->d_render_region_pairs.alloc(std::max<size_t>(1, pairs_region.size()) * 4));
-  HIPCHK(ctx->d_render_all_pairs.alloc(std::max<size_t>(1, pairs_all.size()) * 4));
-  if (!pairs_region.empty())
-    HIPCHK(hipMemcpy(ctx->d_render_region_pairs.p, pairs_region.data(), pairs_region.size() * 4, hipMemcpyHostToDevice));
-  if (!pairs_all.empty())
-    HIPCHK(hipMemcpy(ctx->d_render_all_pairs.p, pairs_all.data(), pairs_all.size() * 4, hipMemcpyHostToDevice));
+  HIPCHK(UploadTable(&ctx->d_render_region_pairs, pairs_region));
+  HIPCHK(UploadTable(&ctx->d_render_all_pairs, pairs_all));
   ctx->n_render_region = int(list_region.size());
   ctx->n_render_all = int(list_all.size());
-  HIPCHK(ctx->d_render_region.alloc(std::max<size_t>(1, list_region.size()) * 4));
-  HIPCHK(ctx->d_render_all.alloc(std::max<size_t>(1, list_all.size()) * 4));
-  if (!list_region.empty())
-    HIPCHK(hipMemcpy(ctx->d_render_region.p, list_region.data(), list_region.size() * 4, hipMemcpyHostToDevice));
-  if (!list_all.empty())
-    HIPCHK(hipMemcpy(ctx->d_render_all.p, list_all.data(), list_all.size() * 4, hipMemcpyHostToDevice));
+  HIPCHK(UploadTable(&ctx->d_render_region, list_region));
+  HIPCHK(UploadTable(&ctx->d_render_all, list_all));
   return M3T_OK;
 }
 
@@ -1522,24 +1407,17 @@ int BuildRoiTables(Ctx* ctx) {
   std::vector<int> first(n_cams + 1, 0);
   for (auto& it : items) ++first[size_t(it.camera) + 1];
   for (size_t c = 0; c < n_cams; ++c) first[c + 1] += first[c];
-  HIPCHK(ctx->d_roi_items.alloc(std::max<size_t>(1, items.size()) * sizeof(RoiItemDev)));
+  HIPCHK(UploadTable(&ctx->d_roi_items, items));
   {  // region modality -> its optimizer (region_histogram_kernel behind a guarded step)
     std::vector<int> opt_of(std::max<size_t>(1, ctx->region_mods.size()), -1);
     for (size_t oi = 0; oi < ctx->opt_table.size(); ++oi)
       if (ctx->opt_table[oi].region_modality >= 0) opt_of[size_t(ctx->opt_table[oi].region_modality)] = int(oi);
-    HIPCHK(ctx->d_roi_opt_of_region.alloc(opt_of.size() * sizeof(int)));
-    HIPCHK(hipMemcpy(ctx->d_roi_opt_of_region.p, opt_of.data(), opt_of.size() * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(UploadTable(&ctx->d_roi_opt_of_region, opt_of));
   }
-  HIPCHK(ctx->d_roi_item_first.alloc(first.size() * sizeof(int)));
-  if (!items.empty())
-    HIPCHK(hipMemcpy(ctx->d_roi_items.p, items.data(), items.size() * sizeof(RoiItemDev), hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(ctx->d_roi_item_first.p, first.data(), first.size() * sizeof(int), hipMemcpyHostToDevice));
+  HIPCHK(UploadTable(&ctx->d_roi_item_first, first));
   ctx->n_roi_items = int(items.size());
-  HIPCHK(ctx->d_roi_motion_peak.alloc(std::max<size_t>(1, items.size()) * sizeof(float)));
-  {  // (until a body's motion is known its margin is the caller's)
-    std::vector<float> peaks(std::max<size_t>(1, items.size()), -1.0f);
-    HIPCHK(hipMemcpy(ctx->d_roi_motion_peak.p, peaks.data(), peaks.size() * sizeof(float), hipMemcpyHostToDevice));
-  }
+  // (until a body's motion is known its margin is the caller's)
+  HIPCHK(UploadTable(&ctx->d_roi_motion_peak, std::vector<float>(std::max<size_t>(1, items.size()), -1.0f)));
   {  // the guard's headers: every object's readers by their rows in the sorted table
     std::vector<float> blocks(ctx->opt_table.size() * per_object, 0.0f);
     for (size_t j = 0; j < items.size(); ++j) {
@@ -1554,36 +1432,23 @@ int BuildRoiTables(Ctx* ctx) {
   {  // the camera ids in order: a batch of consecutive ids needs no list of its own
     std::vector<int> all(std::max<size_t>(1, n_cams));
     for (size_t c = 0; c < n_cams; ++c) all[c] = int(c);
-    HIPCHK(ctx->d_roi_all_cam_ids.alloc(all.size() * sizeof(int)));
-    HIPCHK(hipMemcpy(ctx->d_roi_all_cam_ids.p, all.data(), all.size() * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(UploadTable(&ctx->d_roi_all_cam_ids, all));
   }
   int slots = 1;
   for (auto& c : ctx->cameras) slots = std::max(slots, c->n_slots);
   ctx->roi_rect_slots = slots;
-  HIPCHK(ctx->d_roi_rects.alloc(size_t(slots) * n_cams * sizeof(m3t_roi_rect)));
   ctx->roi_sources.assign(size_t(slots), {});
   HIPCHK(ctx->d_roi_pose_snapshot.alloc(Ctx::kRoiSnapshots * std::max<size_t>(64, ctx->body_poses.size() * 4)));
-  for (auto& e : ctx->roi_snapshot_done)
-    if (!e) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  for (auto& e : ctx->roi_snapshot_done) HIPCHK(e.Ensure(hipEventDisableTiming));
   {  // what every slot holds now: a whole frame, or (a rectangle from before the rebuild) nothing that can be vouched for
     std::vector<m3t_roi_rect> rects(size_t(slots) * n_cams, m3t_roi_empty());
     for (size_t c = 0; c < n_cams; ++c)
       for (int sl = 0; sl < ctx->cameras[c]->n_slots; ++sl)
         if (!ctx->cameras[c]->slot_is_roi[sl])
           rects[size_t(sl) * n_cams + c] = m3t_roi_rect{0, 0, ctx->cameras[c]->intr.width - 1, ctx->cameras[c]->intr.height - 1};
-    HIPCHK(hipMemcpy(ctx->d_roi_rects.p, rects.data(), rects.size() * sizeof(m3t_roi_rect), hipMemcpyHostToDevice));
+    HIPCHK(UploadTable(&ctx->d_roi_rects, rects));
   }
-  if (!ctx->roi_miss_host) {  // two lists in one mapped block: misses (repeated), misses of the repeat
-    void *host = nullptr, *dev = nullptr;
-    const size_t list = Ctx::kRoiMissCapacity + 1;
-    HIPCHK(hipHostMalloc(&host, 2 * list * sizeof(int), hipHostMallocMapped));
-    std::memset(host, 0, 2 * list * sizeof(int));
-    HIPCHK(hipHostGetDevicePointer(&dev, host, 0));
-    ctx->roi_miss_host = static_cast<int*>(host);
-    ctx->roi_miss_dev = static_cast<int*>(dev);
-    ctx->roi_unrecovered_host = ctx->roi_miss_host + list;
-    ctx->roi_unrecovered_dev = ctx->roi_miss_dev + list;
-  }
+  if (!ctx->roi_miss.host) HIPCHK(ctx->roi_miss.Alloc(2 * (Ctx::kRoiMissCapacity + 1) * sizeof(int), kMapped, true));
   return M3T_OK;
 }
 
@@ -1662,22 +1527,17 @@ int UploadTables(Ctx* ctx) {
     }
     if (n_cams && custom) {
       // one table for cameras on different slots, staged through a small pinned ring: no host sync per switch
-      if (ctx->cam_stage_bytes < version_bytes) {
+      if (ctx->cam_staging.SmallestBlock() < version_bytes) {  // all blocks at once, behind everything that read them
         HIPCHK(hipStreamSynchronize(ctx->stream));
-        for (int i = 0; i < Ctx::kStage; ++i) {
-          if (ctx->cam_stage[i]) (void)hipHostFree(ctx->cam_stage[i]);
-          HIPCHK(hipHostMalloc(&ctx->cam_stage[i], version_bytes * 2, hipHostMallocDefault));
-          if (!ctx->cam_stage_done[i]) HIPCHK(hipEventCreateWithFlags(&ctx->cam_stage_done[i], hipEventDisableTiming));
-        }
-        ctx->cam_stage_bytes = version_bytes * 2;
+        HIPCHK(ctx->cam_staging.GrowAll(version_bytes));
       }
-      const int stage = ctx->cam_stage_next;
-      ctx->cam_stage_next = (stage + 1) % Ctx::kStage;
-      HIPCHK(hipEventSynchronize(ctx->cam_stage_done[stage]));  // normally long complete
-      fill(static_cast<CameraDev*>(ctx->cam_stage[stage]), -1);
-      HIPCHK(hipMemcpyAsync(ctx->d_cams.as<uint8_t>() + size_t(n_versions) * version_bytes, ctx->cam_stage[stage],
-                            version_bytes, hipMemcpyHostToDevice, ctx->stream));
-      HIPCHK(hipEventRecord(ctx->cam_stage_done[stage], ctx->stream));
+      void* staged = nullptr;
+      int stage = 0;
+      HIPCHK(ctx->cam_staging.Acquire(version_bytes, &staged, nullptr, &stage));
+      fill(static_cast<CameraDev*>(staged), -1);
+      HIPCHK(hipMemcpyAsync(ctx->d_cams.as<uint8_t>() + size_t(n_versions) * version_bytes, staged, version_bytes,
+                            hipMemcpyHostToDevice, ctx->stream));
+      HIPCHK(ctx->cam_staging.Release(stage, ctx->stream));
     }
     ctx->cams_active = ctx->d_cams.as<CameraDev>() + (custom ? size_t(n_versions) : size_t(uniform_slot)) * n_cams;
     ctx->cams_dirty = false;
@@ -1690,15 +1550,12 @@ int UploadTables(Ctx* ctx) {
     for (size_t i = 0; i < r.size(); ++i) r[i] = ctx->region_mods[i]->dev;
     std::vector<DepthModDev> d(ctx->depth_mods.size());
     for (size_t i = 0; i < d.size(); ++i) d[i] = ctx->depth_mods[i]->dev;
-    HIPCHK(ctx->d_region.alloc(std::max<size_t>(1, r.size()) * sizeof(RegionModDev)));
-    HIPCHK(ctx->d_depth.alloc(std::max<size_t>(1, d.size()) * sizeof(DepthModDev)));
-    if (!r.empty()) HIPCHK(hipMemcpy(ctx->d_region.p, r.data(), r.size() * sizeof(RegionModDev), hipMemcpyHostToDevice));
-    if (!d.empty()) HIPCHK(hipMemcpy(ctx->d_depth.p, d.data(), d.size() * sizeof(DepthModDev), hipMemcpyHostToDevice));
+    HIPCHK(UploadTable(&ctx->d_region, r));
+    HIPCHK(UploadTable(&ctx->d_depth, d));
     if (!ctx->texture_mods.empty()) {
       std::vector<TextureModDev> t(ctx->texture_mods.size());
       for (size_t i = 0; i < t.size(); ++i) t[i] = ctx->texture_mods[i]->dev;
-      HIPCHK(ctx->d_texture.alloc(t.size() * sizeof(TextureModDev)));
-      HIPCHK(hipMemcpy(ctx->d_texture.p, t.data(), t.size() * sizeof(TextureModDev), hipMemcpyHostToDevice));
+      HIPCHK(UploadTable(&ctx->d_texture, t));
     }
     {
       std::vector<TextureModDev> hamming;
@@ -1721,12 +1578,8 @@ int UploadTables(Ctx* ctx) {
       ctx->n_texture_l2 = int(l2.size());
       ctx->n_texture_hamming = int(hamming.size());
       if (!l2.empty()) {
-        HIPCHK(ctx->d_texture_l2.alloc(l2.size() * sizeof(TextureL2Dev)));
-        HIPCHK(hipMemcpy(ctx->d_texture_l2.p, l2.data(), l2.size() * sizeof(TextureL2Dev), hipMemcpyHostToDevice));
-        if (!hamming.empty()) {
-          HIPCHK(ctx->d_texture_hamming.alloc(hamming.size() * sizeof(TextureModDev)));
-          HIPCHK(hipMemcpy(ctx->d_texture_hamming.p, hamming.data(), hamming.size() * sizeof(TextureModDev), hipMemcpyHostToDevice));
-        }
+        HIPCHK(UploadTable(&ctx->d_texture_l2, l2));
+        if (!hamming.empty()) HIPCHK(UploadTable(&ctx->d_texture_hamming, hamming));
         ctx->lds_texture_l2 = texture_l2_lds_bytes(words_max);
         // (the attribute belongs to the function, not to this context: the widest descriptor any context can hold)
         HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(texture_match_l2_kernel),
@@ -1752,10 +1605,7 @@ int UploadTables(Ctx* ctx) {
       detectors.push_back(d);
     }
     ctx->n_detectors = int(detectors.size());
-    if (!detectors.empty()) {
-      HIPCHK(ctx->d_detectors.alloc(detectors.size() * sizeof(TextureDetectorDev)));
-      HIPCHK(hipMemcpy(ctx->d_detectors.p, detectors.data(), detectors.size() * sizeof(TextureDetectorDev), hipMemcpyHostToDevice));
-    }
+    if (!detectors.empty()) HIPCHK(UploadTable(&ctx->d_detectors, detectors));
     // kinematic structures (m3t_links.hip) as soon as one optimizer is more than a free rigid body
     ctx->tree_mode = !ctx->texture_mods.empty();  // a texture modality: the general path, one launch per sub-step
     for (auto& o : ctx->optimizers) {
@@ -1832,10 +1682,7 @@ int UploadTables(Ctx* ctx) {
       int r = BuildRoiTables(ctx);  // (sets RigidOptDev::search_poses)
       if (r) return r;
     }
-    HIPCHK(ctx->d_opts.alloc(std::max<size_t>(1, ctx->opt_table.size()) * sizeof(RigidOptDev)));
-    if (!ctx->opt_table.empty())
-      HIPCHK(hipMemcpy(ctx->d_opts.p, ctx->opt_table.data(), ctx->opt_table.size() * sizeof(RigidOptDev),
-                       hipMemcpyHostToDevice));
+    HIPCHK(UploadTable(&ctx->d_opts, ctx->opt_table));
     ComputeLayout(ctx);
     size_t max_lds = std::max(std::max(ctx->lds_track, ctx->lds_hist), ctx->lds_depth);
     REQUIRE(max_lds <= 160 * 1024, M3T_ERR_UNSUPPORTED,
@@ -1852,48 +1699,32 @@ int UploadTables(Ctx* ctx) {
       if (m->p.n_histogram_bins != ctx->region_mods[0]->p.n_histogram_bins || m->shared_histograms >= 0)
         ctx->lds_compact_table = 0;
     }
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(tracking_step_compact_kernel),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, int(ctx->lds_compact)));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(tracking_step_compact_wide_kernel),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, int(ctx->lds_compact)));
-    if (ctx->lds_compact_table)
-      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(tracking_step_compact_table_kernel),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, int(ctx->lds_compact_table)));
     // the split kernel: free rigid bodies with their own histograms (the pair table is read from L2)
     ctx->split_possible = ctx->fused_possible;
     for (auto& m : ctx->region_mods)
       if (m->shared_histograms >= 0 || m->p.n_histogram_bins < 4) ctx->split_possible = false;
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(tracking_step_split_kernel),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, int(std::max(ctx->lds_track, ctx->lds_hist))));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(tracking_step_split_moments_kernel),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, int(std::max(ctx->lds_track, ctx->lds_hist))));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(tracking_step_split_render_kernel),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, int(std::max(ctx->lds_track, ctx->lds_hist))));
-    for (const void* pair_kernel : {reinterpret_cast<const void*>(tracking_step_split_pair_kernel),
-                                    reinterpret_cast<const void*>(tracking_step_pair_kernel),
-                                    reinterpret_cast<const void*>(tracking_step_lds_pair_kernel)})
-      HIPCHK(hipFuncSetAttribute(pair_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 int(std::max(ctx->lds_track, ctx->lds_hist))));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(tracking_step_kernel),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, int(std::max(ctx->lds_track, ctx->lds_hist))));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(tracking_step_lds_kernel),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, int(std::max(ctx->lds_track, ctx->lds_hist))));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(region_correspondence_kernel),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, int(ctx->lds_corr)));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(region_correspondence_lds_kernel),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, int(ctx->lds_corr)));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(region_gradient_hessian_kernel),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, int(ctx->lds_corr)));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(region_histogram_kernel),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, int(ctx->lds_hist)));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(region_histogram_list_kernel),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, int(ctx->lds_hist)));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(region_histogram_flagged_kernel),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, int(ctx->lds_hist)));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(depth_correspondence_kernel),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, int(ctx->lds_depth)));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(depth_gradient_hessian_kernel),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, int(ctx->lds_depth)));
+    // the dynamic LDS each kernel may be launched with
+    auto fn = [](auto* kernel) { return reinterpret_cast<const void*>(kernel); };
+    using Kernels = std::vector<const void*>;
+    const struct {
+      Kernels kernels;
+      size_t bytes;
+    } lds_groups[] = {
+        {{fn(tracking_step_compact_kernel), fn(tracking_step_compact_wide_kernel)}, ctx->lds_compact},
+        {ctx->lds_compact_table ? Kernels{fn(tracking_step_compact_table_kernel)} : Kernels{}, ctx->lds_compact_table},
+        {{fn(tracking_step_split_kernel), fn(tracking_step_split_moments_kernel), fn(tracking_step_split_render_kernel),
+          fn(tracking_step_split_pair_kernel), fn(tracking_step_pair_kernel), fn(tracking_step_lds_pair_kernel),
+          fn(tracking_step_kernel), fn(tracking_step_lds_kernel)},
+         std::max(ctx->lds_track, ctx->lds_hist)},
+        {{fn(region_correspondence_kernel), fn(region_correspondence_lds_kernel), fn(region_gradient_hessian_kernel)},
+         ctx->lds_corr},
+        {{fn(region_histogram_kernel), fn(region_histogram_list_kernel), fn(region_histogram_flagged_kernel)},
+         ctx->lds_hist},
+        {{fn(depth_correspondence_kernel), fn(depth_gradient_hessian_kernel)}, ctx->lds_depth},
+    };
+    for (const auto& group : lds_groups)
+      for (const void* kernel : group.kernels)
+        HIPCHK(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, int(group.bytes)));
     ctx->tables_dirty = false;
   }
   size_t n_bodies = ctx->body_poses.size() / 16;
@@ -1944,17 +1775,16 @@ int CheckImages(Ctx* ctx) {
 struct ScopedKernelTimer {
   Ctx* ctx;
   int which;
-  hipEvent_t a = nullptr, b = nullptr;
+  EventPair events;
   ScopedKernelTimer(Ctx* c, int w) : ctx(c), which(w) {
     if (ctx->timing_region) ctx->kernel_launches[w] += 1;  // (no event between the launches)
-    if (!ctx->timing) return;
-    if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) { a = b = nullptr; return; }
-    (void)hipEventRecord(a, ctx->stream);
+    if (!ctx->timing || events.Ensure(hipEventDefault) != hipSuccess) return;
+    (void)hipEventRecord(events.a.get(), ctx->stream);
   }
   ~ScopedKernelTimer() {
-    if (!a) return;
-    (void)hipEventRecord(b, ctx->stream);
-    ctx->pending.push_back({a, b, which});
+    if (!events) return;
+    (void)hipEventRecord(events.b.get(), ctx->stream);
+    ctx->pending.push_back({std::move(events), which});
   }
 };
 
@@ -2407,13 +2237,13 @@ long LastRead(Ctx* ctx, const int* ids, int n, int slot) {
 // in a slab and in the host block (rows of row_step bytes): order, transfer, mark ("Frame
 // ingest").  copied: the slot-copied events of the camera or the slab.  The arguments have been validated.
 int UploadWholeFrames(Ctx* ctx, const int* ids, int n, int slot, const void* src, size_t row_step, int cs,
-                      std::vector<hipEvent_t>* copied) {
+                      std::vector<Event>* copied) {
   const Camera& c0 = *ctx->cameras[ids[0]];
   const size_t row = size_t(c0.intr.width) * (c0.is_depth ? 2 : 3);
   HIPCHK(hipSetDevice(ctx->device));
   HIPCHK(ctx->ingest.EnsureStarted(ctx->ingest_cus, ctx->prop.multiProcessorCount));
   HIPCHK(ctx->ingest.OrderCopy(cs, LastRead(ctx, ids, n, slot), ctx->stream));
-  hipStream_t stream = ctx->ingest.Stream(cs);
+  hipStream_t stream = ctx->ingest.CopyStream(cs);
   if (row_step == c0.pitch)  // contiguous on both sides: one linear DMA transfer
     HIPCHK(hipMemcpyAsync(c0.frame(slot), src, c0.frame_bytes * size_t(n) - (c0.pitch - row), hipMemcpyHostToDevice, stream));
   else
@@ -2448,10 +2278,11 @@ int m3t_hip_create(m3t_hip_context** out, int device_id) {
   auto ctx = std::make_unique<m3t_hip_context>();
   ctx->device = device_id;
   if ((e = hipSetDevice(device_id)) != hipSuccess || (e = hipGetDeviceProperties(&ctx->prop, device_id)) != hipSuccess ||
-      (e = CreateMaskedStream(0, ctx->prop.multiProcessorCount, &ctx->stream, false)) != hipSuccess) {
+      (e = CreateMaskedStream(0, ctx->prop.multiProcessorCount, &ctx->compute, false)) != hipSuccess) {
     g_create_error = std::string("device initialisation failed: ") + hipGetErrorString(e);
     return M3T_ERR_DEVICE;
   }
+  ctx->stream = ctx->compute.get();
   ctx->compute_cus = ctx->prop.multiProcessorCount;
   *out = ctx.release();
   return M3T_OK;
@@ -2460,25 +2291,10 @@ int m3t_hip_create(m3t_hip_context** out, int device_id) {
 void m3t_hip_destroy(m3t_hip_context* ctx) {
   if (!ctx) return;
   (void)hipSetDevice(ctx->device);
-  if (ctx->stream) {
-    (void)hipStreamSynchronize(ctx->stream);
-    (void)hipStreamDestroy(ctx->stream);
-  }
-  ctx->ingest.Shutdown();
-  for (int i = 0; i < m3t_hip_context::kStage; ++i) {
-    if (ctx->cam_stage[i]) (void)hipHostFree(ctx->cam_stage[i]);
-    if (ctx->cam_stage_done[i]) (void)hipEventDestroy(ctx->cam_stage_done[i]);
-  }
-  for (auto& c : ctx->cameras)
-    for (auto& e : c->slot_copied)
-      if (e) (void)hipEventDestroy(e);
-  if (ctx->split_abort_host) (void)hipHostFree(ctx->split_abort_host);
-  if (ctx->table_overflow_host) (void)hipHostFree(ctx->table_overflow_host);
-  if (ctx->roi_miss_host) (void)hipHostFree(ctx->roi_miss_host);
-  for (auto& e : ctx->roi_snapshot_done)
-    if (e) (void)hipEventDestroy(e);
-  if (ctx->region_a) (void)hipEventDestroy(ctx->region_a);
-  if (ctx->region_b) (void)hipEventDestroy(ctx->region_b);
+  // nothing is in flight when the members go: the streams drain first, the host buffers are let go behind the copies
+  if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
+  (void)ctx->ingest.SyncCopies();
+  ctx->ingest.UnregisterAll();
   if (ctx->comm && ctx->comm_owned && g_rccl.CommDestroy) (void)g_rccl.CommDestroy(ctx->comm);
   delete ctx;
 }
@@ -2659,12 +2475,12 @@ int m3t_hip_camera_slot_sync(m3t_hip_context* ctx, int id, int slot) {
   HIPCHK(hipSetDevice(ctx->device));
   hipEvent_t slab_copied = nullptr;  // behind the last batch upload / rectangle pull into the slot
   if (c.slab >= 0 && size_t(slot) < ctx->slabs[size_t(c.slab)]->slot_copied.size())
-    slab_copied = ctx->slabs[size_t(c.slab)]->slot_copied[slot];
+    slab_copied = ctx->slabs[size_t(c.slab)]->slot_copied[slot].get();
   if (c.slot_is_roi[slot]) {
     // a rectangle went into the slot (m3t_hip_cameras_upload_batch_roi_async): the host block is read by the pull and,
     // should a body outrun its rectangle, again by the repair of the step that reads the slot -- both must be over
     if (slab_copied) HIPCHK(hipEventSynchronize(slab_copied));
-    else if (ctx->ingest.Stream(0)) HIPCHK(hipStreamSynchronize(ctx->ingest.Stream(0)));
+    else if (ctx->ingest.CopyStream(0)) HIPCHK(hipStreamSynchronize(ctx->ingest.CopyStream(0)));
     HIPCHK(ctx->ingest.WaitForReader(c.last_read_step[slot], ctx->stream));
     return M3T_OK;
   }
@@ -2672,7 +2488,7 @@ int m3t_hip_camera_slot_sync(m3t_hip_context* ctx, int id, int slot) {
   // completed costs nothing to wait for)
   if (slab_copied) HIPCHK(hipEventSynchronize(slab_copied));
   if (size_t(slot) >= c.slot_copied.size() || !c.slot_copied[slot]) return M3T_OK;  // nothing (else) was enqueued
-  HIPCHK(hipEventSynchronize(c.slot_copied[slot]));
+  HIPCHK(hipEventSynchronize(c.slot_copied[slot].get()));
   return M3T_OK;
 }
 // One frame ring for a group of cameras of equal geometry: [slot][camera][frame], so that slot s of the whole group is
@@ -2782,22 +2598,19 @@ int m3t_hip_reserve_ingest_cus(m3t_hip_context* ctx, int n_cus) {
   HIPCHK(hipSetDevice(ctx->device));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   HIPCHK(ctx->ingest.SyncCopies());
-  // all new streams first, then the swap: a failure leaves the context as it was.  (hipExtStreamCreateWithCUMask makes
-  // BLOCKING streams: while CUs are reserved, work on the legacy NULL stream -- a plain hipMemcpy, torch's default
+  // all new streams first, then the swap: a failure leaves the context as it was.  (A stream with a CU mask is a
+  // BLOCKING stream: while CUs are reserved, work on the legacy NULL stream -- a plain hipMemcpy, torch's default
   // stream -- synchronises with the compute stream and copy stream 0; keep such work off the device meanwhile, or
   // the pull / step overlap is lost.)
-  hipStream_t compute = nullptr, copies[Ingest::kCopyStreams] = {nullptr};
+  Stream compute, copies[Ingest::kCopyStreams];
   hipError_t e = CreateMaskedStream(n_cus, ctx->prop.multiProcessorCount, &compute, false);
   if (e == hipSuccess && ctx->ingest.async()) e = Ingest::CreateStreams(n_cus, ctx->prop.multiProcessorCount, copies);
   if (e != hipSuccess) {
     (void)hipGetLastError();
-    if (compute) (void)hipStreamDestroy(compute);
-    for (hipStream_t made : copies)
-      if (made) (void)hipStreamDestroy(made);
     return Fail(ctx, M3T_ERR_UNSUPPORTED, "this device / runtime does not create CU-masked streams");
   }
-  (void)hipStreamDestroy(ctx->stream);
-  ctx->stream = compute;
+  ctx->compute = std::move(compute);
+  ctx->stream = ctx->compute.get();
   ctx->ingest.ReplaceStreams(copies);
   ctx->ingest_cus = n_cus;
   ctx->compute_cus = ctx->prop.multiProcessorCount - n_cus;
@@ -2840,7 +2653,7 @@ int m3t_hip_cameras_upload_batch_roi_async(m3t_hip_context* ctx, const int* ids,
   if (!pull) return m3t_hip_cameras_upload_batch_async(ctx, ids, n, slot, base, camera_stride, row_step);
   HIPCHK(hipSetDevice(ctx->device));
   const int cs = 0;
-  hipStream_t copy_stream = ctx->ingest.Stream(cs);
+  hipStream_t copy_stream = ctx->ingest.CopyStream(cs);
   bool consecutive = true;
   for (int i = 0; i < n; ++i) consecutive = consecutive && ids[i] == ids[0] + i;
   const int* d_ids = ctx->d_roi_all_cam_ids.as<int>() + ids[0];
@@ -2868,9 +2681,9 @@ int m3t_hip_cameras_upload_batch_roi_async(m3t_hip_context* ctx, const int* ids,
     d_ids = list->as<int>();
   }
   HIPCHK(ctx->ingest.OrderCopy(cs, LastRead(ctx, ids, n, slot), ctx->stream));
-  HIPCHK(hipStreamWaitEvent(copy_stream, ctx->roi_snapshot_done[ctx->roi_use], 0));  // the poses the rectangles come from
+  HIPCHK(hipStreamWaitEvent(copy_stream, ctx->roi_snapshot_done[ctx->roi_use].get(), 0));  // the poses the rectangles come from
   const bool adaptive = ctx->roi_adaptive && ctx->roi_prev >= 0;
-  if (adaptive) HIPCHK(hipStreamWaitEvent(copy_stream, ctx->roi_snapshot_done[ctx->roi_prev], 0));
+  if (adaptive) HIPCHK(hipStreamWaitEvent(copy_stream, ctx->roi_snapshot_done[ctx->roi_prev].get(), 0));
   const Camera& c0 = *ctx->cameras[ids[0]];
   // the camera table is only read for intrinsics and world2camera here: any slot version will do (the first one)
   m3t_roi_rect* rects = ctx->d_roi_rects.as<m3t_roi_rect>() + size_t(slot) * ctx->cameras.size();
@@ -2913,6 +2726,18 @@ int m3t_hip_cameras_upload_batch_roi_async(m3t_hip_context* ctx, const int* ids,
   }
   return M3T_OK;
 }
+// one of the two lists of the mapped miss block, read in place behind the stream and cleared
+static int ReadRoiMisses(Ctx* ctx, bool unrecovered, int* bodies, int capacity, int* n) {
+  if (!ctx->roi_miss.host) return M3T_OK;
+  HIPCHK(hipSetDevice(ctx->device));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  int* list = Ctx::RoiMissList(ctx->roi_miss.host, unrecovered);
+  const int count = __atomic_load_n(&list[0], __ATOMIC_ACQUIRE);
+  *n = count;
+  for (int i = 0; i < std::min(std::min(count, capacity), int(Ctx::kRoiMissCapacity)); ++i) bodies[i] = list[1 + i];
+  std::memset(list, 0, (Ctx::kRoiMissCapacity + 1) * sizeof(int));
+  return M3T_OK;
+}
 // Bodies whose steps since the last call needed pixels outside the rectangle that had been uploaded: up to `capacity`
 // body ids, *n = how many there were; the list is cleared.  Such a step is not committed; the library fetched the whole
 // frames and repeated it (m3t_hip_execute_tracking_step), so the poses ARE the whole-frame poses -- the list says how
@@ -2922,14 +2747,7 @@ int m3t_hip_roi_get_status(m3t_hip_context* ctx, int* bodies, int capacity, int*
   REQUIRE(n && capacity >= 0 && (bodies || capacity == 0), M3T_ERR_INVALID_ARGUMENT, "null output");
   *n = 0;
   if (n_rectangle_uploads) *n_rectangle_uploads = ctx->roi_pulls;
-  if (!ctx->roi_miss_host) return M3T_OK;
-  HIPCHK(hipSetDevice(ctx->device));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  const int count = __atomic_load_n(&ctx->roi_miss_host[0], __ATOMIC_ACQUIRE);
-  *n = count;
-  for (int i = 0; i < std::min(std::min(count, capacity), int(Ctx::kRoiMissCapacity)); ++i) bodies[i] = ctx->roi_miss_host[1 + i];
-  std::memset(ctx->roi_miss_host, 0, (Ctx::kRoiMissCapacity + 1) * sizeof(int));
-  return M3T_OK;
+  return ReadRoiMisses(ctx, false, bodies, capacity, n);
 }
 // Bodies whose step left its rectangle AND whose repeat did too (the whole frames were not within reach: the host
 // block of the upload was not recorded for the slot, e.g. after the tables were rebuilt).  Their step was not
@@ -2940,14 +2758,7 @@ int m3t_hip_roi_get_unrecovered(m3t_hip_context* ctx, int* bodies, int capacity,
   CHECK_CTX();
   REQUIRE(n && capacity >= 0 && (bodies || capacity == 0), M3T_ERR_INVALID_ARGUMENT, "null output");
   *n = 0;
-  if (!ctx->roi_unrecovered_host) return M3T_OK;
-  HIPCHK(hipSetDevice(ctx->device));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  const int count = __atomic_load_n(&ctx->roi_unrecovered_host[0], __ATOMIC_ACQUIRE);
-  *n = count;
-  for (int i = 0; i < std::min(std::min(count, capacity), int(Ctx::kRoiMissCapacity)); ++i) bodies[i] = ctx->roi_unrecovered_host[1 + i];
-  std::memset(ctx->roi_unrecovered_host, 0, (Ctx::kRoiMissCapacity + 1) * sizeof(int));
-  return M3T_OK;
+  return ReadRoiMisses(ctx, true, bodies, capacity, n);
 }
 int m3t_hip_ingest_sync(m3t_hip_context* ctx) {
   CHECK_CTX();
@@ -3261,9 +3072,8 @@ int m3t_hip_modalities_get_gradient_hessian(m3t_hip_context* ctx, float* out, in
     std::vector<const float*> src(size_t(n), nullptr);
     for (int i = 0; i < n; ++i) src[size_t(i)] = ModalityGh(ctx, i);
     HIPCHK(hipStreamSynchronize(ctx->stream));
-    HIPCHK(ctx->d_gh_sources.alloc(size_t(n) * sizeof(float*)));
+    HIPCHK(UploadTable(&ctx->d_gh_sources, src));
     HIPCHK(ctx->d_gh_all.alloc(size_t(n) * 42 * sizeof(float)));
-    HIPCHK(hipMemcpy(ctx->d_gh_sources.p, src.data(), size_t(n) * sizeof(float*), hipMemcpyHostToDevice));
     ctx->gh_sources_count = n;
   }
   hipLaunchKernelGGL(gather_gradient_hessian_kernel, dim3(n), dim3(42), 0, ctx->stream,
@@ -4407,9 +4217,9 @@ int m3t_hip_start_modalities(m3t_hip_context* ctx, int iteration) {
     }
   }
   if ((r = Prepare(ctx, true))) return r;
-  if (ctx->table_overflow_host) {  // new histograms: the LDS pair table gets its chance again
+  if (ctx->table_overflow.host) {  // new histograms: the LDS pair table gets its chance again
     HIPCHK(hipStreamSynchronize(ctx->stream));
-    *static_cast<volatile unsigned*>(ctx->table_overflow_host) = 0u;
+    *ctx->table_overflow.as<volatile unsigned>() = 0u;
   }
   if ((r = RenderForModalities(ctx, true))) return r;  // start_modality_renderer_ptrs tracker.cpp:430-436
   if ((r = LaunchTextureDetection(ctx))) return r;  // StartModality :319
@@ -4627,20 +4437,14 @@ int BuildJudgeTables(Ctx* ctx, Judge* j) {
   j->n_parts = int(parts.size());
   j->n_add_bodies = int(add_bodies.size());
   j->n_add_parts = int(add_parts.size());
-  HIPCHK(j->d_bodies.alloc(bodies.size() * sizeof(JudgeBodyDev)));
-  HIPCHK(j->d_parts.alloc(std::max<size_t>(1, parts.size()) * sizeof(JudgePartDev)));
+  HIPCHK(UploadTable(&j->d_bodies, bodies));
+  HIPCHK(UploadTable(&j->d_parts, parts));
   HIPCHK(j->d_partial.alloc(std::max<size_t>(1, parts.size()) * 2 * sizeof(double)));
   HIPCHK(j->d_flags.alloc(size_t(n) * sizeof(int)));
-  HIPCHK(hipMemcpy(j->d_bodies.p, bodies.data(), bodies.size() * sizeof(JudgeBodyDev), hipMemcpyHostToDevice));
-  if (!parts.empty())
-    HIPCHK(hipMemcpy(j->d_parts.p, parts.data(), parts.size() * sizeof(JudgePartDev), hipMemcpyHostToDevice));
   if (!add_bodies.empty()) {
-    HIPCHK(j->d_add_bodies.alloc(add_bodies.size() * sizeof(JudgeAddBodyDev)));
-    HIPCHK(j->d_add_parts.alloc(add_parts.size() * sizeof(JudgePartDev)));
+    HIPCHK(UploadTable(&j->d_add_bodies, add_bodies));
+    HIPCHK(UploadTable(&j->d_add_parts, add_parts));
     HIPCHK(j->d_add_partial.alloc(add_parts.size() * sizeof(double)));
-    HIPCHK(hipMemcpy(j->d_add_bodies.p, add_bodies.data(), add_bodies.size() * sizeof(JudgeAddBodyDev),
-                     hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(j->d_add_parts.p, add_parts.data(), add_parts.size() * sizeof(JudgePartDev), hipMemcpyHostToDevice));
   }
   HIPCHK(hipMemset(j->d_flags.p, 0, size_t(n) * sizeof(int)));
   return M3T_OK;
@@ -4666,11 +4470,8 @@ int m3t_hip_judge_create(m3t_hip_context* ctx, const int* body_ids, int n_bodies
   j->add_only.assign(size_t(n_bodies), 0);
   j->targets.assign(size_t(n_bodies), -1);
   j->geometry2body.resize(size_t(n_bodies));
-  j->row_done.assign(size_t(n_rows_max), nullptr);
-  const size_t bytes = size_t(n_bodies) * size_t(n_rows_max) * sizeof(m3t_body_judgement);
-  HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&j->rows_host), bytes, hipHostMallocMapped));
-  std::memset(j->rows_host, 0, bytes);
-  HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&j->rows_dev), j->rows_host, 0));
+  j->row_done.resize(size_t(n_rows_max));
+  HIPCHK(j->rows.Alloc(size_t(n_bodies) * size_t(n_rows_max) * sizeof(m3t_body_judgement), kMapped, true));
   if ((r = BuildJudgeTables(ctx, j.get()))) return r;
   ctx->judges.push_back(std::move(j));
   *judge = int(ctx->judges.size()) - 1;
@@ -4696,8 +4497,7 @@ int m3t_hip_judge_set_vertices(m3t_hip_context* ctx, int judge, int index, const
   const std::vector<float> padded = PadVertices(xyz, n_vertices, 4);
   HIPCHK(hipStreamSynchronize(ctx->stream));  // earlier calls may still search the old vertices
   auto mem = std::make_unique<DevMem>();
-  HIPCHK(mem->alloc(padded.size() * 4));
-  HIPCHK(hipMemcpy(mem->p, padded.data(), padded.size() * 4, hipMemcpyHostToDevice));
+  HIPCHK(UploadTable(mem.get(), padded));
   j->vertices[size_t(index)] = std::move(mem);
   j->n_vertices[size_t(index)] = n_vertices;
   return BuildJudgeTables(ctx, j);
@@ -4827,9 +4627,8 @@ int m3t_hip_judge_bodies(m3t_hip_context* ctx, int judge, const float* gt_body2w
   const int *d_region_ids = args.region_ids.in<int>(dev), *d_region_body = args.region_body.in<int>(dev),
             *d_region_first = args.region_first.in<int>(dev);
   const int row_index = j->n_rows;
-  m3t_body_judgement* d_row = j->rows_dev + size_t(row_index) * size_t(n);
-  if (!j->row_done[size_t(row_index)])
-    HIPCHK(hipEventCreateWithFlags(&j->row_done[size_t(row_index)], hipEventDisableTiming));
+  m3t_body_judgement* d_row = j->rows.dev_as<m3t_body_judgement>() + size_t(row_index) * size_t(n);
+  HIPCHK(j->row_done[size_t(row_index)].Ensure(hipEventDisableTiming));
   if (j->n_add_parts > 0) {  // the ADD-only bodies: workgroups of their own (m3t_opt.hip)
     hipLaunchKernelGGL(judge_add_only_kernel, dim3(unsigned(j->n_add_parts)), dim3(M3T_JUDGE_THREADS), 0, ctx->stream,
                        ctx->d_poses.as<float>(), j->d_add_bodies.as<JudgeAddBodyDev>(), j->d_add_parts.as<JudgePartDev>(),
@@ -4875,10 +4674,10 @@ int m3t_hip_judge_bodies(m3t_hip_context* ctx, int judge, const float* gt_body2w
                        d_structure_ints, d_structure_ints + j->n_structures + 1,
                        d_structure_ints + j->n_structures + 1 + j->structure_groups + 1,
                        j->d_structure_thresholds.as<float>(), j->n_structures,
-                       j->structure_rows_dev + size_t(row_index) * size_t(j->n_structures));
+                       j->structure_rows.dev_as<m3t_structure_judgement>() + size_t(row_index) * size_t(j->n_structures));
   }
   if ((r = EndEnqueued(ctx, &j->args, slot, reset ? &reads.cameras : nullptr))) return r;
-  HIPCHK(hipEventRecord(j->row_done[size_t(row_index)], ctx->stream));
+  HIPCHK(hipEventRecord(j->row_done[size_t(row_index)].get(), ctx->stream));
   if (reset) ctx->roi_end_valid = false;  // the host's mirror does not vouch for these bodies' poses any more
   ++j->n_rows;
   if (row) *row = row_index;
@@ -4931,9 +4730,9 @@ int m3t_hip_judge_read(m3t_hip_context* ctx, int judge, int first_row, int n_row
   if (n_rows == 0) return M3T_OK;
   REQUIRE(out, M3T_ERR_INVALID_ARGUMENT, "judge_read: null output");
   HIPCHK(hipSetDevice(ctx->device));
-  HIPCHK(hipEventSynchronize(j->row_done[size_t(first_row + n_rows - 1)]));  // rows complete in order
+  HIPCHK(hipEventSynchronize(j->row_done[size_t(first_row + n_rows - 1)].get()));  // rows complete in order
   const size_t n = j->body_ids.size();
-  std::memcpy(out, j->rows_host + size_t(first_row) * n, size_t(n_rows) * n * sizeof(m3t_body_judgement));
+  std::memcpy(out, j->rows.as<m3t_body_judgement>() + size_t(first_row) * n, size_t(n_rows) * n * sizeof(m3t_body_judgement));
   return M3T_OK;
 }
 // RTBEvaluator's ids_combined_bodies_ of n_structures structures: structure s holds the groups
@@ -4973,17 +4772,12 @@ int m3t_hip_judge_set_structures(m3t_hip_context* ctx, int judge, int n_structur
   ints.insert(ints.end(), structure_first_group, structure_first_group + n_structures + 1);
   ints.insert(ints.end(), group_first_index, group_first_index + n_groups + 1);
   ints.insert(ints.end(), listed_body_indices, listed_body_indices + n_listed);
-  HIPCHK(j->d_structure_ints.alloc(ints.size() * 4));
+  HIPCHK(UploadTable(&j->d_structure_ints, ints));
   HIPCHK(j->d_structure_thresholds.alloc(size_t(n_structures) * 4));
-  HIPCHK(hipMemcpy(j->d_structure_ints.p, ints.data(), ints.size() * 4, hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(j->d_structure_thresholds.p, error_thresholds, size_t(n_structures) * 4, hipMemcpyHostToDevice));
-  if (j->structure_rows_host) HIPCHK(hipHostFree(j->structure_rows_host));
-  j->structure_rows_host = j->structure_rows_dev = nullptr;
   j->n_structures = 0;
-  const size_t bytes = size_t(n_structures) * size_t(j->n_rows_max) * sizeof(m3t_structure_judgement);
-  HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&j->structure_rows_host), bytes, hipHostMallocMapped));
-  std::memset(j->structure_rows_host, 0, bytes);
-  HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&j->structure_rows_dev), j->structure_rows_host, 0));
+  HIPCHK(j->structure_rows.Alloc(size_t(n_structures) * size_t(j->n_rows_max) * sizeof(m3t_structure_judgement),
+                                 kMapped, true));
   j->n_structures = n_structures;
   j->structure_groups = size_t(n_groups);
   return M3T_OK;
@@ -4998,9 +4792,9 @@ int m3t_hip_judge_read_structures(m3t_hip_context* ctx, int judge, int first_row
   if (n_rows == 0) return M3T_OK;
   REQUIRE(out, M3T_ERR_INVALID_ARGUMENT, "judge_read_structures: null output");
   HIPCHK(hipSetDevice(ctx->device));
-  HIPCHK(hipEventSynchronize(j->row_done[size_t(first_row + n_rows - 1)]));  // rows complete in order
+  HIPCHK(hipEventSynchronize(j->row_done[size_t(first_row + n_rows - 1)].get()));  // rows complete in order
   const size_t n = size_t(j->n_structures);
-  std::memcpy(out, j->structure_rows_host + size_t(first_row) * n, size_t(n_rows) * n * sizeof(m3t_structure_judgement));
+  std::memcpy(out, j->structure_rows.as<m3t_structure_judgement>() + size_t(first_row) * n, size_t(n_rows) * n * sizeof(m3t_structure_judgement));
   return M3T_OK;
 }
 // OPTEvaluator::CalculatePoseResults for listed body `index` from now on (m3t_hip.h).  Waits for the stream and uploads:
@@ -5041,9 +4835,8 @@ int m3t_hip_vertices_diameter(m3t_hip_context* ctx, const float* xyz, int n_vert
   const std::vector<float> padded = PadVertices(xyz, n_vertices, M3T_DIAMETER_TILE);
   HIPCHK(hipStreamSynchronize(ctx->stream));
   DevMem vertices, max_bits;
-  HIPCHK(vertices.alloc(padded.size() * 4));
+  HIPCHK(UploadTable(&vertices, padded));
   HIPCHK(max_bits.alloc(sizeof(unsigned int)));
-  HIPCHK(hipMemcpy(vertices.p, padded.data(), padded.size() * 4, hipMemcpyHostToDevice));
   HIPCHK(hipMemset(max_bits.p, 0, sizeof(unsigned int)));
   for (size_t first = 0; first < n_tiles; first += M3T_DIAMETER_ROW_TILES_PER_LAUNCH) {
     ScopedKernelTimer timer(ctx, 1);
@@ -5308,7 +5101,7 @@ void LaunchTree(Ctx* ctx, K kernel, int grid, size_t lds, int iteration, Tail...
 // the exchange buffers and the per-launch descriptor of a split launch
 int PrepareSplit(Ctx* ctx, int n, int parts, SplitParams* out) {
   const size_t per_object = size_t(2) * M3T_SPLIT_LANES * 32;  // granules
-  int r = MappedWord(ctx, &ctx->split_abort_host, &ctx->split_abort_dev);
+  int r = MappedWord(ctx, &ctx->split_abort);
   if (r) return r;
   if (ctx->split_objects < size_t(n) || ctx->split_seq >= (1u << 26) - 1) {
     HIPCHK(hipStreamSynchronize(ctx->stream));
@@ -5323,7 +5116,7 @@ int PrepareSplit(Ctx* ctx, int n, int parts, SplitParams* out) {
   SplitParams sp{};
   sp.granules = ctx->d_split.as<unsigned long long>();
   sp.object_abort = reinterpret_cast<unsigned*>(sp.granules + ctx->split_objects * per_object);
-  sp.host_abort = ctx->split_abort_dev;
+  sp.host_abort = ctx->split_abort.dev_as<unsigned>();
   sp.seq = ctx->split_seq;
   if (++ctx->split_launches == 0) ctx->split_launches = 1;  // (0 = the word's initial value)
   sp.abort_id = ctx->split_launches;
@@ -5342,13 +5135,13 @@ int StepRigidFused(Ctx* ctx, int iteration, const StepOverrides& overrides, bool
   const int n = int(ctx->opt_table.size());
   ScopedKernelTimer timer(ctx, 0);
   m3t_step::RigidStepFacts facts = RigidFacts(ctx, roi_frames);
-  if (ctx->table_overflow_host) facts.table_overflow = *static_cast<volatile unsigned*>(ctx->table_overflow_host);
+  if (ctx->table_overflow.host) facts.table_overflow = *ctx->table_overflow.as<volatile unsigned>();
   const m3t_step::RigidStepPlan plan = m3t_step::PlanRigidStep(
       facts, overrides, [ctx](StepKernel k, int threads, size_t lds) { return ResidentStepBlocks(ctx, k, threads, lds); });
   int r = M3T_OK;
   if (plan.compact_table) {
-    if ((r = MappedWord(ctx, &ctx->table_overflow_host, &ctx->table_overflow_dev))) return r;
-    ctx->compact_table.table_overflow = ctx->table_overflow_dev;
+    if ((r = MappedWord(ctx, &ctx->table_overflow))) return r;
+    ctx->compact_table.table_overflow = ctx->table_overflow.dev_as<unsigned>();
   }
   report->kernel = plan.kernel;
   // a step that reads rectangles runs the guarded kernels (m3t_kernels.hip, roi_guard_outside): an object whose poses
@@ -5362,9 +5155,9 @@ int StepRigidFused(Ctx* ctx, int iteration, const StepOverrides& overrides, bool
     guard.n_rect_slots = ctx->roi_rect_slots;
     guard.n_poses = ctx->roi_n_poses;
     guard.mode = 1;
-    guard.misses = ctx->roi_miss_dev;
+    guard.misses = Ctx::RoiMissList(ctx->roi_miss.dev, false);
     guard.miss_capacity = int(Ctx::kRoiMissCapacity);
-    guard.unrecovered = ctx->roi_unrecovered_dev;
+    guard.unrecovered = Ctx::RoiMissList(ctx->roi_miss.dev, true);
   }
   const int grid = plan.grid(n), threads = plan.threads, n_corr = ctx->n_corr_iterations;
   const size_t lds = plan.lds;
@@ -5489,7 +5282,7 @@ int StepTreeFused(Ctx* ctx, int iteration, const StepOverrides& overrides, StepR
   const bool want_fused_histogram = !ctx->region_mods.empty() && ctx->hist_counts_in_lds && ctx->shared_histograms.empty() &&
                                     !overrides.no_fused_histogram;
   const size_t lds = TreeStepLds(ctx, want_fused_histogram);
-  int r = MappedWord(ctx, &ctx->split_abort_host, &ctx->split_abort_dev);
+  int r = MappedWord(ctx, &ctx->split_abort);
   if (r) return r;
   if (ctx->tree_seq >= (1u << 26) - 1) {  // the tags restart: clear them first
     HIPCHK(hipStreamSynchronize(ctx->stream));
@@ -5500,7 +5293,7 @@ int StepTreeFused(Ctx* ctx, int iteration, const StepOverrides& overrides, StepR
   xp.seq = ++ctx->tree_seq;
   if (++ctx->split_launches == 0) ctx->split_launches = 1;
   xp.abort_id = ctx->split_launches;
-  xp.host_abort = ctx->split_abort_dev;
+  xp.host_abort = ctx->split_abort.dev_as<unsigned>();
   // Structures that leave CUs idle (the 8-body chain: 8 workgroups on 256 CUs): several workgroups per tracked link
   // (tracking_step_tree_split_kernel; open structures only -- the constrained kernel keeps one).  The parts of a link
   // exchange their lines' results, so all workgroups must be resident: checked like the split kernel's launch.
@@ -5660,7 +5453,7 @@ int m3t_hip_execute_tracking_step(m3t_hip_context* ctx, int iteration) {
       ctx->roi_prev = -1;
       ctx->roi_use = 0;
       HIPCHK(hipMemcpyAsync(roi_snapshots, ctx->d_poses.p, ctx->body_poses.size() * 4, hipMemcpyDeviceToDevice, ctx->stream));
-      HIPCHK(hipEventRecord(ctx->roi_snapshot_done[0], ctx->stream));
+      HIPCHK(hipEventRecord(ctx->roi_snapshot_done[0].get(), ctx->stream));
     }
     ctx->roi_snapshot_valid = true;
   }
@@ -5697,7 +5490,7 @@ int m3t_hip_execute_tracking_step(m3t_hip_context* ctx, int iteration) {
     while (ctx->roi_end_index == ctx->roi_use || ctx->roi_end_index == ctx->roi_prev) ++ctx->roi_end_index;
     HIPCHK(hipMemcpyAsync(roi_snapshots + size_t(ctx->roi_end_index) * roi_snapshot_floats, ctx->d_poses.p,
                           ctx->body_poses.size() * 4, hipMemcpyDeviceToDevice, ctx->stream));
-    HIPCHK(hipEventRecord(ctx->roi_snapshot_done[ctx->roi_end_index], ctx->stream));
+    HIPCHK(hipEventRecord(ctx->roi_snapshot_done[ctx->roi_end_index].get(), ctx->stream));
     ctx->roi_end_valid = true;
   }
   HIPCHK(ctx->ingest.MarkRead(ctx->stream, ctx->cameras, nullptr));  // the current slot of every camera
@@ -5726,21 +5519,14 @@ int m3t_hip_set_kernel_timing(m3t_hip_context* ctx, int enable) {
   CHECK_CTX();
   HIPCHK(hipSetDevice(ctx->device));
   HIPCHK(hipStreamSynchronize(ctx->stream));
-  for (auto& p : ctx->pending) {
-    (void)hipEventDestroy(p.a);
-    (void)hipEventDestroy(p.b);
-  }
   ctx->pending.clear();
   ctx->timing = enable == 1;
   ctx->timing_region = enable == 2;
   ctx->kernel_ms[0] = ctx->kernel_ms[1] = 0.0;
   ctx->kernel_launches[0] = ctx->kernel_launches[1] = 0;
   if (ctx->timing_region) {  // the stream is idle (synchronised above): the region starts here
-    if (!ctx->region_a) {
-      HIPCHK(hipEventCreate(&ctx->region_a));
-      HIPCHK(hipEventCreate(&ctx->region_b));
-    }
-    HIPCHK(hipEventRecord(ctx->region_a, ctx->stream));
+    HIPCHK(ctx->region.Ensure(hipEventDefault));
+    HIPCHK(hipEventRecord(ctx->region.a.get(), ctx->stream));
   }
   return M3T_OK;
 }
@@ -5755,18 +5541,15 @@ int m3t_hip_debug_log_checksum(m3t_hip_context* ctx, unsigned first_bits, unsign
   CHECK_CTX();
   REQUIRE(out && first_bits <= last_bits, M3T_ERR_INVALID_ARGUMENT, "bad range");
   HIPCHK(hipSetDevice(ctx->device));
-  unsigned long long* d = nullptr;
-  HIPCHK(hipMalloc(reinterpret_cast<void**>(&d), 24));
-  hipError_t e = hipMemsetAsync(d, 0, 24, ctx->stream);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(log_checksum_kernel, dim3(ctx->prop.multiProcessorCount * 8), dim3(256), 0, ctx->stream,
-                       first_bits, last_bits, d);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipMemcpyAsync(out, d, 24, hipMemcpyDeviceToHost, ctx->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-  (void)hipFree(d);
-  HIPCHK(e);
+  DevMem sums;  // (a failure leaves through its destructor, which waits for the device)
+  HIPCHK(sums.alloc(24));
+  unsigned long long* d = sums.as<unsigned long long>();
+  HIPCHK(hipMemsetAsync(d, 0, 24, ctx->stream));
+  hipLaunchKernelGGL(log_checksum_kernel, dim3(ctx->prop.multiProcessorCount * 8), dim3(256), 0, ctx->stream,
+                     first_bits, last_bits, d);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(out, d, 24, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
   return M3T_OK;
 }
 int m3t_hip_comm_get_allreduce_count(m3t_hip_context* ctx, long long* count) {
@@ -5803,10 +5586,10 @@ int m3t_hip_get_kernel_timing(m3t_hip_context* ctx, float total_ms[2], int launc
   CHECK_CTX();
   HIPCHK(hipSetDevice(ctx->device));
   if (ctx->timing_region) {  // device time from the enabling call to here, all of it booked on the tracking launches
-    HIPCHK(hipEventRecord(ctx->region_b, ctx->stream));
+    HIPCHK(hipEventRecord(ctx->region.b.get(), ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     float ms = 0.0f;
-    HIPCHK(hipEventElapsedTime(&ms, ctx->region_a, ctx->region_b));
+    HIPCHK(hipEventElapsedTime(&ms, ctx->region.a.get(), ctx->region.b.get()));
     if (total_ms) { total_ms[0] = ms; total_ms[1] = 0.0f; }
     if (launches) { launches[0] = ctx->kernel_launches[0]; launches[1] = ctx->kernel_launches[1]; }
     return M3T_OK;
@@ -5814,12 +5597,10 @@ int m3t_hip_get_kernel_timing(m3t_hip_context* ctx, float total_ms[2], int launc
   HIPCHK(hipStreamSynchronize(ctx->stream));
   for (auto& p : ctx->pending) {
     float ms = 0.0f;
-    if (hipEventElapsedTime(&ms, p.a, p.b) == hipSuccess) {
+    if (hipEventElapsedTime(&ms, p.events.a.get(), p.events.b.get()) == hipSuccess) {
       ctx->kernel_ms[p.which] += ms;
       ctx->kernel_launches[p.which] += 1;
     }
-    (void)hipEventDestroy(p.a);
-    (void)hipEventDestroy(p.b);
   }
   ctx->pending.clear();
   if (total_ms) { total_ms[0] = float(ctx->kernel_ms[0]); total_ms[1] = float(ctx->kernel_ms[1]); }

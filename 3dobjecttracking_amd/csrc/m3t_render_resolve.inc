@@ -74,7 +74,7 @@
   __syncthreads();
   const int n_out = (row_hi - row_lo + 1) * S;
   // four pixels per thread and store where the band allows it (its first pixel and its length multiples of four: the
-  // images come from hipMalloc): one 8-byte and one 4-byte store instead of four 2-byte and four 1-byte ones -- the
+  // images are DevMem blocks): one 8-byte and one 4-byte store instead of four 2-byte and four 1-byte ones -- the
   // output of 128 pairs cost 10.7 of the launch's 69 us (round 5, probe builds)
   const RendererDev* t = twin >= 0 ? &renderers[twin] : nullptr;  // the same rendering with the twin's id byte: the
   const size_t first = (size_t)row_lo * S;                        // winner's draw order sits in bits 8..15
