@@ -14,7 +14,8 @@
 //                             the whole ExecuteTrackingStep loop nest fused on device
 //   tracking_step_split_kernel the same with 4 / 8 / 16 workgroups per object (batches that leave CUs idle)
 //   tracking_step_split_moments_kernel the split kernel for Region-only objects whose first Newton step behind a search
-//                             is a global one: the lines' means and variances cross first, the distributions beside the solve
+//                             is a global one: the lines' means and variances cross first, the distributions beside the solve;
+//                             at 512 threads that step's Jacobians are formed while the moments travel
 //   (kinematic structures: m3t_links.hip)
 //
 // Arithmetic follows the reference expression by expression in IEEE f32
@@ -1385,6 +1386,66 @@ __device__ __forceinline__ void chain_sums(const float* rows_a, int pitch_a, int
 // RegionModality::CalculateGradientAndHessian (:485-558), the per-line part: one thread per line slot
 // writes the line's 27 products to rows[row * pitch + line] (zeros for slots that do not contribute).
 // ---------------------------------------------------------------------------
+// The line's expressions stand ONCE, as pieces (macros over the locals m, cam, b2c, it, s, nl, line, rows, pitch, ok, J,
+// wg, wh): region_products strings them in the reference's order, and tracking_step_split_moments_kernel runs the
+// pieces that need the pose and phase A's rows only (region_products_head) beside its moments wait and the rest
+// (region_products_tail) behind it.  Pieces and not two functions called by region_products: as head() followed by tail()
+// every kernel that calls region_products came out with other machine code (profiles/r16_products_head_early.txt).
+// What a piece needs in scope (besides m, cam, b2c, it, s, nl, line) and what it declares or sets for the ones after it:
+//   M3T_PRODUCTS_LINE        needs -;                                             declares cx cy cz, x y z, normal_u/v,
+//                                                                                 center_u/v, ncts
+//   M3T_PRODUCTS_VARIANCE    needs -;                                             declares measured_variance
+//   M3T_PRODUCTS_DELTA       needs LINE;                                          declares fu_z fv_z xfu_z yfv_z, delta_cs
+//   M3T_PRODUCTS_DLL_GLOBAL  needs a declared dll, delta_cs, measured_variance;   sets dll
+//   M3T_PRODUCTS_JACOBIAN    needs a declared J[6], LINE, DELTA (fu_z fv_z xfu_z yfv_z); sets J, declares dc0..2, t0..2, weight
+//   M3T_PRODUCTS_WEIGHTS     needs declared wg wh, weight, dll, measured_variance; sets wg, wh
+//   M3T_PRODUCTS_STORES      needs ok, J, wg, wh, rows, pitch;                    declares out
+// (the tail takes J, delta_cs and weight from the head's registers instead of LINE / DELTA / JACOBIAN)
+#define M3T_PRODUCTS_LINE /* :497-513 */                                                                             \
+  float cx = s.state[LS_CX * nl + line], cy = s.state[LS_CY * nl + line], cz = s.state[LS_CZ * nl + line];          \
+  float x, y, z;                                                                                                     \
+  apply_pose(b2c, cx, cy, cz, x, y, z);                                                                              \
+  float normal_u = s.state[LS_NORMAL_U * nl + line], normal_v = s.state[LS_NORMAL_V * nl + line];                    \
+  float center_u = s.state[LS_CENTER_U * nl + line], center_v = s.state[LS_CENTER_V * nl + line];                    \
+  float ncts = s.state[LS_NCTS * nl + line];
+#define M3T_PRODUCTS_VARIANCE float measured_variance = s.state[LS_VAR * nl + line];
+#define M3T_PRODUCTS_DELTA                                                                                           \
+  float fu_z = cam.fu / z;                                                                                           \
+  float fv_z = cam.fv / z;                                                                                           \
+  float xfu_z = x * fu_z;                                                                                            \
+  float yfv_z = y * fv_z;                                                                                            \
+  float delta_cs = (normal_u * (xfu_z + cam.ppu - center_u) + normal_v * (yfv_z + cam.ppv - center_v) -              \
+                    s.state[LS_DELTA_R * nl + line]) *                                                               \
+                   ncts;
+#define M3T_PRODUCTS_DLL_GLOBAL dll = (s.state[LS_MEAN * nl + line] - delta_cs) / measured_variance;
+#define M3T_PRODUCTS_JACOBIAN /* t: RowVector3f * Matrix3f (body2camera_rotation_) */                                \
+  float dc0 = ncts * normal_u * fu_z;                                                                                \
+  float dc1 = ncts * normal_v * fv_z;                                                                                \
+  float dc2 = ncts * (-normal_u * xfu_z - normal_v * yfv_z) / z;                                                     \
+  float t0 = (dc0 * b2c.l[0] + dc1 * b2c.l[1]) + dc2 * b2c.l[2];                                                     \
+  float t1 = (dc0 * b2c.l[3] + dc1 * b2c.l[4]) + dc2 * b2c.l[5];                                                     \
+  float t2 = (dc0 * b2c.l[6] + dc1 * b2c.l[7]) + dc2 * b2c.l[8];                                                     \
+  J[0] = cy * t2 - cz * t1;                                                                                          \
+  J[1] = cz * t0 - cx * t2;                                                                                          \
+  J[2] = cx * t1 - cy * t0;                                                                                          \
+  J[3] = t0;                                                                                                         \
+  J[4] = t1;                                                                                                         \
+  J[5] = t2;                                                                                                         \
+  float weight = m.min_expected_variance / (ncts * ncts * it.variance);
+#define M3T_PRODUCTS_WEIGHTS                                                                                         \
+  wg = weight * dll;                                                                                                 \
+  wh = weight / measured_variance;
+// gradient_ += (weight * dll) * J^T; hessian_ (lower) -= ((w / var) J^T) J
+#define M3T_PRODUCTS_STORES                                                                                          \
+  float* out = rows + line;                                                                                          \
+  if (ok) {                                                                                                          \
+    _Pragma("unroll") for (int r = 0; r < 6; ++r) out[r * pitch] = -(wg * J[r]);                                     \
+    int k = 6;                                                                                                       \
+    _Pragma("unroll") for (int c = 0; c < 6; ++c)                                                                    \
+      _Pragma("unroll") for (int r = c; r < 6; ++r) out[(k++) * pitch] = (wh * J[r]) * J[c];                         \
+  } else {                                                                                                           \
+    _Pragma("unroll") for (int k = 0; k < 27; ++k) out[k * pitch] = 0.0f;                                            \
+  }
 // (tid0 / nt0: the threads that take part -- all of the workgroup, or the half that works beside depth_products' half)
 __device__ __forceinline__ void region_products(CRegion& m, CCam& cam, const Affine& b2c, int corr_iteration, int opt_iteration,
                                 const Lds& s, float* rows, int pitch, int tid0 = -1, int nt0 = 0) {
@@ -1394,25 +1455,14 @@ __device__ __forceinline__ void region_products(CRegion& m, CCam& cam, const Aff
   for (int line = tid; line < slots; line += nt) {
     float J[6], wg = 0.0f, wh = 0.0f;
     bool ok = false;
-    if (line < nl && (f2i_bits(s.state[LS_VALID * nl + line]) & 1)) {  // :497-513
+    if (line < nl && (f2i_bits(s.state[LS_VALID * nl + line]) & 1)) {
       ok = true;
-      float cx = s.state[LS_CX * nl + line], cy = s.state[LS_CY * nl + line], cz = s.state[LS_CZ * nl + line];
-      float x, y, z;
-      apply_pose(b2c, cx, cy, cz, x, y, z);
-      float normal_u = s.state[LS_NORMAL_U * nl + line], normal_v = s.state[LS_NORMAL_V * nl + line];
-      float center_u = s.state[LS_CENTER_U * nl + line], center_v = s.state[LS_CENTER_V * nl + line];
-      float ncts = s.state[LS_NCTS * nl + line];
-      float measured_variance = s.state[LS_VAR * nl + line];
-      float fu_z = cam.fu / z;
-      float fv_z = cam.fv / z;
-      float xfu_z = x * fu_z;
-      float yfv_z = y * fv_z;
-      float delta_cs = (normal_u * (xfu_z + cam.ppu - center_u) + normal_v * (yfv_z + cam.ppv - center_v) -
-                        s.state[LS_DELTA_R * nl + line]) *
-                       ncts;
+      M3T_PRODUCTS_LINE
+      M3T_PRODUCTS_VARIANCE
+      M3T_PRODUCTS_DELTA
       float dll = 0.0f;
       if (opt_iteration < m.n_global_iterations) {
-        dll = (s.state[LS_MEAN * nl + line] - delta_cs) / measured_variance;
+        M3T_PRODUCTS_DLL_GLOBAL
       } else {
         int upper = f2i(delta_cs + m.distribution_length_plus_1_half);
         int lower = upper - 1;
@@ -1434,38 +1484,59 @@ __device__ __forceinline__ void region_products(CRegion& m, CCam& cam, const Aff
           dll = (log_upper - log_lower) * m.learning_rate / measured_variance;
         }
       }
-      float dc0 = ncts * normal_u * fu_z;
-      float dc1 = ncts * normal_v * fv_z;
-      float dc2 = ncts * (-normal_u * xfu_z - normal_v * yfv_z) / z;
-      // RowVector3f * Matrix3f (body2camera_rotation_)
-      float t0 = (dc0 * b2c.l[0] + dc1 * b2c.l[1]) + dc2 * b2c.l[2];
-      float t1 = (dc0 * b2c.l[3] + dc1 * b2c.l[4]) + dc2 * b2c.l[5];
-      float t2 = (dc0 * b2c.l[6] + dc1 * b2c.l[7]) + dc2 * b2c.l[8];
-      J[0] = cy * t2 - cz * t1;
-      J[1] = cz * t0 - cx * t2;
-      J[2] = cx * t1 - cy * t0;
-      J[3] = t0;
-      J[4] = t1;
-      J[5] = t2;
-      float weight = m.min_expected_variance / (ncts * ncts * it.variance);
-      wg = weight * dll;
-      wh = weight / measured_variance;
+      M3T_PRODUCTS_JACOBIAN
+      M3T_PRODUCTS_WEIGHTS
     }
-    float* out = rows + line;
-    if (ok) {
-#pragma unroll
-      for (int r = 0; r < 6; ++r) out[r * pitch] = -(wg * J[r]);  // gradient_ += (weight * dll) * J^T
-      int k = 6;
-#pragma unroll
-      for (int c = 0; c < 6; ++c)
-#pragma unroll
-        for (int r = c; r < 6; ++r) out[(k++) * pitch] = (wh * J[r]) * J[c];  // hessian_ (lower) -= ((w / var) J^T) J
-    } else {
-#pragma unroll
-      for (int k = 0; k < 27; ++k) out[k * pitch] = 0.0f;
-    }
+    M3T_PRODUCTS_STORES
   }
 }
+// The same pieces for ONE line slot of a global step (opt_iteration < n_global_iterations), in two halves:
+//   head  what needs the pose and phase A's rows only: J, delta_cs, weight, and whether the line is valid.  No LDS write.
+//   tail  what needs the line's mean and variance: dll, wg, wh, the 27 products, the row stores.
+struct RegionLineHead {
+  float J[6], delta_cs, weight;
+  bool ok;
+};
+__device__ __forceinline__ RegionLineHead region_products_head(CRegion& m, CCam& cam, const Affine& b2c, const RegionIter& it,
+                                                               const Lds& s, int line) {
+  const int nl = s.nl;
+  RegionLineHead h;
+  h.ok = false;
+  if (line < nl && (f2i_bits(s.state[LS_VALID * nl + line]) & 1)) {
+    h.ok = true;
+    float J[6];
+    M3T_PRODUCTS_LINE
+    M3T_PRODUCTS_DELTA
+    M3T_PRODUCTS_JACOBIAN
+#pragma unroll
+    for (int r = 0; r < 6; ++r) h.J[r] = J[r];
+    h.delta_cs = delta_cs;
+    h.weight = weight;
+  }
+  return h;
+}
+__device__ __forceinline__ void region_products_tail(const Lds& s, int line, const RegionLineHead& h, float* rows, int pitch) {
+  const int nl = s.nl;
+  const bool ok = h.ok;
+  float J[6], wg = 0.0f, wh = 0.0f;
+  if (ok) {
+#pragma unroll
+    for (int r = 0; r < 6; ++r) J[r] = h.J[r];
+    const float delta_cs = h.delta_cs, weight = h.weight;
+    float dll;
+    M3T_PRODUCTS_VARIANCE
+    M3T_PRODUCTS_DLL_GLOBAL
+    M3T_PRODUCTS_WEIGHTS
+  }
+  M3T_PRODUCTS_STORES
+}
+#undef M3T_PRODUCTS_LINE
+#undef M3T_PRODUCTS_VARIANCE
+#undef M3T_PRODUCTS_DELTA
+#undef M3T_PRODUCTS_DLL_GLOBAL
+#undef M3T_PRODUCTS_JACOBIAN
+#undef M3T_PRODUCTS_WEIGHTS
+#undef M3T_PRODUCTS_STORES
 
 // ---------------------------------------------------------------------------
 // Line results of the workgroups that share one object (tracking_step_split_kernel).
@@ -1745,11 +1816,13 @@ __device__ __forceinline__ bool split_exchange_abort_check(const SplitExchange& 
   }
   return true;
 }
-// the other parts' means and variances: thread -> (part q, element l) as in split_exchange_collect, one granule per
-// thread at 512 threads (two at 256).  A received value is stored where region_moments would have stored one: for
-// valid lines.  Returns false when the exchange timed out (block-uniform); ends with a barrier.
-__device__ __forceinline__ bool split_exchange_collect_moments(const SplitExchange& x, int round, CRegion& m, const Lds& s) {
-  const int tid = threadIdx.x, nt = blockDim.x, nl = s.nl;
+// the other parts' means and variances, by the threads from first_thread on (a multiple of 256 of them): thread ->
+// (part q, element l) as in split_exchange_collect, one granule per thread with 512 collectors, two with 256 (both
+// loads issued before the first tag is looked at).  A received value is stored where region_moments would have stored
+// one: for valid lines.  No barrier; returns whether a wait ran out (the caller joins: split_exchange_abort_check).
+__device__ __forceinline__ bool split_exchange_collect_moments(const SplitExchange& x, int round, CRegion& m, const Lds& s,
+                                                               int first_thread) {
+  const int tid = (int)threadIdx.x - first_thread, nt = (int)blockDim.x - first_thread, nl = s.nl;
   const int lshift = x.lshift, n_parts = x.n_parts, per_part = x.per_part_lines, part = x.part;
   const uint32_t seq = x.seq, tag = seq * 64u + (uint32_t)round + 1u;
   auto* const object_abort = x.object_abort;
@@ -1775,7 +1848,7 @@ __device__ __forceinline__ bool split_exchange_collect_moments(const SplitExchan
     g1 = split_exchange_wait(object_abort, seq, tag, theirs + ((size_t)j1 << lshift), g1, timed_out);
     if (valid) s.state[(j1 == 0 ? LS_MEAN : LS_VAR) * nl + e] = __int_as_float(static_cast<int>(static_cast<uint32_t>(g1)));
   }
-  return split_exchange_abort_check(x, timed_out);
+  return timed_out;
 }
 // the other parts' distribution rows, by the threads from first_thread on (whole waves) while the first wave runs the
 // chain and the solve: item i = field (i / 256) of lane (i % 256), the field index wave-uniform; batches of eight
@@ -3300,6 +3373,13 @@ struct SplitParams {               // tracking_step_split_kernel: n_parts workgr
 };
 
 extern "C++" {
+// tracking_step_split_moments_kernel: whether a search's first products run in two halves around the moments wait (512
+// threads: waves 4-7 have no line and collect; every product slot has a thread).  A function of launch constants, asked
+// where it is needed: a variable for it in tracking_step_body's loop scopes would be a variable (and a clean-up at every
+// `return` in them) in every instantiation, which changed the other split kernels' machine code.
+__device__ __forceinline__ bool products_head_early(int n_update_iterations, int nl) {
+  return (int)blockDim.x >= 2 * M3T_SPLIT_LANES && n_update_iterations >= 1 && chain_slots(nl) <= M3T_SPLIT_LANES;
+}
 // PAIR (round 6; the _pair_ kernels, for batches whose bodies carry a RegionModality AND a DepthModality): per Newton step
 // the lines' products by the first half of the workgroup BESIDE the points' products by the second (one round instead of
 // two: 200 lines and 200 points never fill 512 threads one after the other), and the two modalities' sums on two waves --
@@ -3431,9 +3511,39 @@ __device__ __forceinline__ void tracking_step_body(const RigidOptDev* opts, cons
         region_distribution_rows(exchange, c, *rm, s, line_lo, line_hi, walked);
         EXCHANGE_STAMP(1, c, part, object);
         PHASE_MARK(33);  // the row pass (in place of phases C1, C2 and the owner moments, row 30)
-        if (!split_exchange_collect_moments(exchange, c, *rm, s)) return;
+        // 512 threads: the lines' threads form what the first Newton step's products need of the pose and phase A's
+        // rows (region_products_head: no LDS write -- the product rows alias seg_f / seg_b, which other waves' row
+        // passes still read) while the waves without a line collect the moments; the pose in LDS is the one the search
+        // started at, so the head's bits are those of the products of u = 0
+        const bool early = products_head_early(n_update_iterations, s.nl);
+        RegionLineHead head{};
+        bool timed_out = false;
+        if (early) {
+          if ((int)threadIdx.x < M3T_SPLIT_LANES) {
+            const Affine b2c = mul_pose(load_pose(cam->world2camera), load_pose(pose));
+            // (an opaque copy of the thread index, here and at the tail: the lines' LDS addresses are formed where they
+            // are used -- formed once in front of the searches they stay live through the pixel walk and spill)
+            int line = threadIdx.x;
+            asm volatile("" : "+v"(line));
+            if (line < chain_slots(s.nl)) head = region_products_head(*rm, *cam, b2c, region_iter(*rm, c), s, line);
+            PHASE_MARK(34);  // products head (beside the moments wait)
+          } else {
+            timed_out = split_exchange_collect_moments(exchange, c, *rm, s, M3T_SPLIT_LANES);
+          }
+        } else {
+          timed_out = split_exchange_collect_moments(exchange, c, *rm, s, 0);
+        }
+        if (!split_exchange_abort_check(exchange, timed_out)) return;
         EXCHANGE_STAMP(2, c, part, object);
         PHASE_MARK(31);  // moments wait
+        if (early) {
+          // the products of u = 0 (a global step: the host vouches n_global_iterations >= 1), what is left of them; nothing
+          // lies between here and their place in the Newton loop, which skips them.  Every slot has a thread.
+          int line = threadIdx.x;
+          asm volatile("" : "+v"(line));
+          if (line < chain_slots(s.nl)) region_products_tail(s, line, head, rows_r, layout.pitch_r);
+          PHASE_MARK(35);  // products tail (u = 0); row 5 keeps the barrier behind it
+        }
       } else if constexpr (SPLIT) {
         PHASE_T0();
         // with occlusion handling on, the flags of the own lines (their occlusion results) travel too and the vote
@@ -3489,9 +3599,17 @@ __device__ __forceinline__ void tracking_step_body(const RigidOptDev* opts, cons
         }
       }
       if (!side_by_side) {
+      if constexpr (MOMENTS_FIRST) {
+        // (rm is not null here: the host admits Region-only objects to this instantiation, as the search's block says)
+        if (u > 0 || !products_head_early(n_update_iterations, s.nl)) {  // (else: done behind the moments' barrier)
+          const Affine b2c = mul_pose(load_pose(cam->world2camera), b2w);
+          region_products(*rm, *cam, b2c, c, u, s, rows_r, layout.pitch_r);
+        }
+      } else {
       if (rm) {
         const Affine b2c = mul_pose(load_pose(cam->world2camera), b2w);
         region_products(*rm, *cam, b2c, c, u, s, rows_r, layout.pitch_r);
+      }
       }
       if (dm) {
         const Affine b2c = mul_pose(load_pose(dcam->world2camera), b2w);

@@ -41,9 +41,13 @@ names = ["view search", "phase A (lines)", "phase B (pixels)", "phase C1 (dist)"
 # Row 33: the row pass of tracking_step_split_moments_kernel (region_distribution_rows) -- distributions, moments and their
 # granules row by row, in place of "phase C1", "phase C2" and "owner moments" (rows 3, 4 and 30: their sum in a library
 # from before the pass is what row 33 compares with)
+# Rows 34, 35 (512 threads): the products of a search's first Newton step in two halves -- the head on the lines' waves
+# while waves 4-7 collect the moments (wave 0's; "moments wait" is what is left of the wait behind it, up to the same
+# barrier as before), the tail behind that barrier; "g/H products + barrier (u=0, global)" keeps the barrier behind the tail
 extra = {30: "owner moments + their granules", 31: "moments wait (round trip + barrier)",
-         32: "  deferred collect (collecting wave)", 33: "row pass (dist + moments + granules)"}
-tot = sum(buf[i] for i in range(7)) + buf[16] + sum(buf[22:27]) + buf[30] + buf[31] + buf[33]
+         32: "  deferred collect (collecting wave)", 33: "row pass (dist + moments + granules)",
+         34: "products head (beside the moments wait)", 35: "products tail (u = 0)"}
+tot = sum(buf[i] for i in range(7)) + buf[16] + sum(buf[22:27]) + buf[30] + buf[31] + sum(buf[33:36])
 for i, nme in enumerate(names):
     print("%-38s %10.0f cycles/frame  %5.1f%%" % (nme, buf[i] / n, 100.0 * buf[i] / tot))
 for i, nme in sorted(extra.items()):
