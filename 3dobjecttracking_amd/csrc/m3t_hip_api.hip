@@ -26,6 +26,7 @@
 #include "m3t_view_rows.h"
 #include "m3t_step_plan.h"
 #include "m3t_render_plan.h"
+#include "m3t_texture_plan.h"
 #include "m3t_call_args.h"
 #include "m3t_ingest_plan.h"
 #include "m3t_kernels.hip"
@@ -46,12 +47,18 @@
 #undef M3T_TEXTURE_LIST_KERNELS
 // the matcher of L2-norm descriptors, behind those again
 #include "m3t_texture_l2.hip"
+// the tiled form of the Hamming matcher, behind that
+#include "m3t_texture_tiled.hip"
 
 static_assert(m3t_step::kBlockThreads == M3T_BLOCK_THREADS && m3t_step::kCompactThreads == M3T_COMPACT_THREADS &&
                   m3t_step::kSplitLanes == M3T_SPLIT_LANES && m3t_step::kSplitMaxParts == M3T_SPLIT_MAX_PARTS &&
                   m3t_step::kMiscBytes == M3T_MISC_FLOATS * 4,
               "m3t_step_plan.h and m3t_device.h disagree");
 static_assert(m3t_render::kBlockThreads == M3T_BLOCK_THREADS, "m3t_render_plan.h and m3t_device.h disagree");
+static_assert(m3t_texture::kMatchThreads == M3T_TEXTURE_MATCH_THREADS && m3t_texture::kQueryTile == M3T_TEXTURE_QUERY_TILE &&
+                  m3t_texture::kMaxFeatures == M3T_TEXTURE_MAX_FEATURES && m3t_texture::kQueryTiles == kTiledQueryTiles &&
+                  m3t_texture::kMaxKeyframes == M3T_TEXTURE_MAX_KEYFRAMES && m3t_texture::kBestBytes == 3 * sizeof(uint32_t),
+              "m3t_texture_plan.h and m3t_texture.h disagree");
 
 namespace {
 
@@ -266,6 +273,7 @@ struct TextureMod {  // TextureModality behind its feature detector (m3t_texture
   m3t_texture_detector_params detector{};
   DevMem focused, scores, boxes, detector_header;
   // L2-norm descriptors (m3t_texture_l2.hip): descriptor_bytes / 4 floats a row, and the matcher's best-two scratch
+  // (which a Hamming modality has too once its context has resolved to the tiled matcher, m3t_texture_tiled.hip)
   bool l2 = false;
   DevMem best;
 };
@@ -397,6 +405,13 @@ struct m3t_hip_context {
   DevMem d_texture_hamming, d_texture_l2;
   int n_texture_hamming = 0, n_texture_l2 = 0, l2_keyframes_max = 0;
   size_t lds_texture_l2 = 0;
+  // The Hamming matcher's form (m3t_texture_plan.h): the mode (the developer override M3T_HIP_TEXTURE_MATCH, looked at
+  // once, when the context is made), the plan in effect, and the table of the Hamming modalities' scratch pointers in
+  // the order of the table the matcher runs on.  The plan is made again by UploadTables whenever the tables changed.
+  int texture_match_mode = m3t_texture::ReadMatchOverride(), hamming_keyframes_max = 0;
+  bool texture_plan_stale = true;
+  m3t_texture::MatchPlan texture_plan{};
+  DevMem d_texture_best;
   int n_detectors = 0;
   DevMem d_cams, d_region, d_depth, d_texture, d_opts, d_poses, d_scratch_view;
   DevMem d_gh_sources, d_gh_all;  // m3t_hip_modalities_get_gradient_hessian
@@ -1562,10 +1577,13 @@ int UploadTables(Ctx* ctx) {
       std::vector<TextureL2Dev> l2;
       int words_max = 0;
       ctx->l2_keyframes_max = 0;
+      ctx->hamming_keyframes_max = 0;
+      ctx->texture_plan_stale = true;
       for (size_t i = 0; i < ctx->texture_mods.size(); ++i) {
         TextureMod& m = *ctx->texture_mods[i];
         if (!m.l2) {
           hamming.push_back(m.dev);
+          ctx->hamming_keyframes_max = std::max(ctx->hamming_keyframes_max, m.dev.n_keyframes_max);
           continue;
         }
         TextureL2Dev d{};
@@ -1727,6 +1745,19 @@ int UploadTables(Ctx* ctx) {
         HIPCHK(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, int(group.bytes)));
     ctx->tables_dirty = false;
   }
+  if (ctx->texture_plan_stale) {  // the Hamming matcher's form; the tiled one needs its scratch (m3t_texture_plan.h)
+    ctx->texture_plan = m3t_texture::PlanMatch(ctx->texture_match_mode, ctx->n_texture_hamming, ctx->hamming_keyframes_max);
+    if (ctx->texture_plan.form == m3t_texture::kTiled) {
+      std::vector<uint32_t*> best;
+      for (auto& m : ctx->texture_mods) {
+        if (m->l2) continue;
+        if (m->best.bytes < ctx->texture_plan.scratch_bytes) HIPCHK(m->best.alloc(ctx->texture_plan.scratch_bytes));
+        best.push_back(m->best.as<uint32_t>());
+      }
+      HIPCHK(UploadTable(&ctx->d_texture_best, best));
+    }
+    ctx->texture_plan_stale = false;
+  }
   size_t n_bodies = ctx->body_poses.size() / 16;
   if (ctx->pose_capacity < n_bodies) {
     // keep device poses if they are newer than the host mirror
@@ -1833,22 +1864,32 @@ int LaunchTextureKeyframes(Ctx* ctx, bool decide) {
 
 int LaunchCorrespondences(Ctx* ctx, int iteration, int corr_iteration) {
   int nr = int(ctx->region_mods.size()), nd = int(ctx->depth_mods.size());
-  if (const int nt = int(ctx->texture_mods.size())) {
+  if (!ctx->texture_mods.empty()) {
     if (corr_iteration == 0) {  // :334
       const int r = LaunchTextureDetection(ctx);
       if (r) return r;
     }
     const int match = corr_iteration == 0 ? 1 : 0;
-    if (ctx->n_texture_l2 == 0) {
-      hipLaunchKernelGGL(texture_match_kernel, dim3(nt), dim3(M3T_TEXTURE_MATCH_THREADS), 0, ctx->stream,
-                         ctx->d_texture.as<TextureModDev>(), ctx->cams_active, ctx->d_poses.as<float>(), match);
-    } else {
-      // the Hamming matcher sees the Hamming modalities alone; the L2 modalities' match is tiled over keyframes and
-      // queries (texture_match_l2_kernel, which finds on the device what it has to do) with the ratio test, the data
-      // points and the projection behind it -- at corr_iteration > 0 the projection alone
-      if (ctx->n_texture_hamming)
-        hipLaunchKernelGGL(texture_match_kernel, dim3(ctx->n_texture_hamming), dim3(M3T_TEXTURE_MATCH_THREADS), 0, ctx->stream,
-                           ctx->d_texture_hamming.as<TextureModDev>(), ctx->cams_active, ctx->d_poses.as<float>(), match);
+    // the Hamming matcher sees the Hamming modalities alone: the whole table, or beside L2 modalities their own one;
+    // its form -- one workgroup a modality, or tiled over ring slots and queries with the collect pass behind it, which
+    // at corr_iteration > 0 runs alone -- is the plan's (m3t_texture_plan.h, made by UploadTables)
+    const m3t_texture::MatchPlan& plan = ctx->texture_plan;
+    const TextureModDev* hamming = (ctx->n_texture_l2 == 0 ? ctx->d_texture : ctx->d_texture_hamming).as<TextureModDev>();
+    if (plan.form == m3t_texture::kOneWorkgroup) {
+      hipLaunchKernelGGL(texture_match_kernel, dim3(plan.match.x, plan.match.y), dim3(M3T_TEXTURE_MATCH_THREADS), 0, ctx->stream,
+                         hamming, ctx->cams_active, ctx->d_poses.as<float>(), match);
+    } else if (plan.form == m3t_texture::kTiled) {
+      uint32_t* const* best = ctx->d_texture_best.as<uint32_t*>();
+      if (match)
+        hipLaunchKernelGGL(texture_match_tiled_kernel, dim3(plan.match.x, plan.match.y), dim3(M3T_TEXTURE_MATCH_THREADS), 0,
+                           ctx->stream, hamming, best);
+      hipLaunchKernelGGL(texture_collect_kernel, dim3(plan.collect.x, plan.collect.y), dim3(M3T_TEXTURE_MATCH_THREADS), 0,
+                         ctx->stream, hamming, best, ctx->cams_active, ctx->d_poses.as<float>(), match);
+    }
+    if (ctx->n_texture_l2) {
+      // the L2 modalities' match is tiled over keyframes and queries (texture_match_l2_kernel, which finds on the device
+      // what it has to do) with the ratio test, the data points and the projection behind it -- at corr_iteration > 0
+      // the projection alone
       const TextureL2Dev* l2 = ctx->d_texture_l2.as<TextureL2Dev>();
       if (match)
         hipLaunchKernelGGL(texture_match_l2_kernel, dim3(ctx->n_texture_l2, ctx->l2_keyframes_max * kL2QueryTiles),

@@ -20,6 +20,7 @@
 #define M3T_TEXTURE_MAX_DESCRIPTOR_WORDS 16  /* 64 bytes: BRISK, FREAK; ORB has 8 */
 #define M3T_TEXTURE_MATCH_THREADS 256        /* query descriptors per pass of texture_match_kernel */
 #define M3T_TEXTURE_TRAIN_TILE 128           /* train descriptors per LDS tile: 8 KB at 64 bytes */
+#define M3T_TEXTURE_QUERY_TILE 64            /* query descriptors per workgroup of texture_match_tiled_kernel: a lane each */
 #define M3T_TEXTURE_ROI_MARGIN 10            /* kRegionOfInterestMargin, texture_modality.h:132 */
 #define M3T_TEXTURE_GH_CHUNK 504             /* data points per pass of the g/H chains (a multiple of 24): 54 KB of rows */
 
@@ -96,6 +97,14 @@ M3T_TEX_FN void m3t_tex_best2_update(m3t_tex_best2* b, int distance, int index) 
   } else if (distance < b->d1) {
     b->d1 = distance;
   }
+}
+// `later` holds the best two of train descriptors that all follow those of `b` (m3t_texture_tiled.hip: the ranges of the
+// four waves): its best is a candidate, then its second, which can at most become the second here, so its index is
+// never needed.  An entry that is not there (INT32_MAX) is smaller than nothing and changes nothing.  The result is
+// what one pass over both ranges in ascending index gives.
+M3T_TEX_FN void m3t_tex_best2_append(m3t_tex_best2* b, const m3t_tex_best2* later) {
+  m3t_tex_best2_update(b, later->d0, later->i0);
+  m3t_tex_best2_update(b, later->d1, -1);
 }
 // :364-367: a query becomes a data point iff it has two matches and NOT d0 / d1 >= threshold (0 / 0 = NaN: kept)
 M3T_TEX_FN bool m3t_tex_ratio_keeps(const m3t_tex_best2* b, float threshold) {

@@ -739,6 +739,27 @@ def _rbot_texture_modality(api, body, camera, texture_parameters, detector_param
     return modality
 
 
+def _dataset_texture_modality(api, body, color, depth, texture_parameters, detector_parameters):
+    """The texture modality of the YCB and OPT evaluators (ycb_evaluator.cpp:476-492, opt_evaluator.cpp:314-326): a
+    RendererGeometry with the body, a FocusedSilhouetteRenderer on the colour camera with id type BODY that references
+    it, TextureModality(body, colour camera, silhouette) -- with MeasureOcclusions(depth camera) where `depth` is given
+    -- and the library's built-in detector in ORB's place.  The caller puts it on the optimizer behind the region and
+    the depth modality (modality_ptrs()[2], ycb_evaluator.cpp:625), and has refused the oracle's context before."""
+    from . import host
+    geometry = host.RendererGeometry(api)
+    geometry.AddBody(body)
+    silhouette = host.FocusedSilhouetteRenderer(api, geometry, color, id_type=0,
+                                                image_size=texture_parameters["focused_image_size"])
+    silhouette.AddReferencedBody(body)
+    if depth is not None:
+        modality = host.TextureModality(api, body, color, silhouette, depth_camera=depth, measure_occlusions=1,
+                                        **texture_parameters)
+    else:
+        modality = host.TextureModality(api, body, color, silhouette, **texture_parameters)
+    modality.SetDetector(**detector_parameters)
+    return modality
+
+
 def _evaluate_rbot_dataset_batched(open_context, dataset_directory, external_directory, body_names, sequence_names,
                                    n_frames, region_parameters, model_parameters, tikhonov_parameter_rotation,
                                    tikhonov_parameter_translation, n_corr_iterations, n_update_iterations, report,
@@ -860,6 +881,14 @@ YCB_DEPTH_PARAMETERS = dict(  # evaluate_ycb_dataset.cpp:66-76
     considered_distances=[0.07, 0.05, 0.04], standard_deviations=[0.05, 0.03, 0.02],
     measured_depth_offset_radius=0.01, measured_occlusion_radius=0.01, measured_occlusion_threshold=0.03,
     n_unoccluded_iterations=0)
+# the fields of evaluate_ycb_dataset.cpp:77-107 that the modality has (its detector is the library's own, not ORB:
+# orb_n_features = 300 becomes the built-in detector's n_features, the ORB pyramid has no counterpart)
+YCB_TEXTURE_PARAMETERS = dict(
+    focused_image_size=200, descriptor_distance_threshold=0.7, tukey_norm_constant=20.0,
+    standard_deviations=[10.0, 10.0, 3.0],
+    max_keyframe_rotation_difference=float(F(10.0) * F(np.pi) / F(180.0)), max_keyframe_age=1000, n_keyframes=1,
+    measured_occlusion_radius=0.01, measured_occlusion_threshold=0.03)
+YCB_DETECTOR_PARAMETERS = dict(n_features=300)  # set_orb_n_features(300), :86; the FAST threshold is the built-in's own
 YCB_MODEL_PARAMETERS = dict(sphere_radius=0.8, n_divides=4, n_points=500, max_radius_depth_offset=0.05,
                             stride_depth_offset=0.002, use_random_seed=False, image_size=2000)  # :1131-1146
 
@@ -906,7 +935,8 @@ def evaluate_ycb_dataset(open_context, dataset_directory, external_directory, se
                          use_matlab_gt_poses=True, n_vertices_evaluation=1000, region_parameters=None,
                          depth_parameters=None, model_parameters=None, tikhonov_parameter_rotation=1000.0,
                          tikhonov_parameter_translation=30000.0, n_corr_iterations=4, n_update_iterations=2,
-                         report=None, shard=(0, 1), judge_on_device=False):
+                         report=None, shard=(0, 1), judge_on_device=False, use_texture_modality=False,
+                         texture_parameters=None, detector_parameters=None, measure_occlusions_texture=True):
     """YCBEvaluator::SetUp + Evaluate with the region and the depth modality, measured occlusions, one run per
     (sequence, body present in it) (CreateRunConfigurations :1006-1022): bodies `dataset/models/<body>/textured.obj`
     in metres, frames `dataset/data/<sequence>/NNNNNN-{color,depth}.png` (depth scale 1e-4), keyframes from
@@ -914,11 +944,19 @@ def evaluate_ycb_dataset(open_context, dataset_directory, external_directory, se
     dataset's own `poses/<body>.txt`), models under `external/models/`.  Returns {(sequence, body): average} and
     the averages over all frames of all runs (CalculateAverageResult).  shard = (rank, world): every world-th run
     (see evaluate_rbot_dataset); the overall averages then cover this process's runs.
-    judge_on_device (HIP library): ADD / ADD-S on the device (evaluate_ycb_sequence)."""
+    judge_on_device (HIP library): ADD / ADD-S on the device (evaluate_ycb_sequence).
+    use_texture_modality (HIP library; set_use_texture_modality(true), evaluate_ycb_dataset.cpp:125-133): every run also
+    gets the texture modality of ycb_evaluator.cpp:476-492 (_dataset_texture_modality) with YCB_TEXTURE_PARAMETERS
+    overridden by `texture_parameters`, measured occlusions on the depth camera unless measure_occlusions_texture is
+    False, and the library's BUILT-IN DETECTOR (YCB_DETECTOR_PARAMETERS overridden by `detector_parameters`) -- not
+    ORB: the reference's configuration with another detector, whose AUC is not claimed to equal the reference's.  The
+    modality stands on the optimizer behind the region and the depth modality.  With the oracle's context: ValueError."""
     import os
 
     from . import config as cfg
     from . import generator, host
+    texture_parameters = dict(YCB_TEXTURE_PARAMETERS, **(texture_parameters or {}))
+    detector_parameters = dict(YCB_DETECTOR_PARAMETERS, **(detector_parameters or {}))
     region_parameters = dict(YCB_REGION_PARAMETERS, **(region_parameters or {}))
     depth_parameters = dict(YCB_DEPTH_PARAMETERS, **(depth_parameters or {}))
     model_parameters = dict(YCB_MODEL_PARAMETERS, **(model_parameters or {}))
@@ -933,6 +971,8 @@ def evaluate_ycb_dataset(open_context, dataset_directory, external_directory, se
     for sequence, name in runs[shard[0]::shard[1]]:
         keyframes = ycb_keyframes(dataset_directory, sequence)
         api = open_context()
+        if use_texture_modality and not getattr(api, "is_hip", True):  # (before a model is read or generated)
+            raise ValueError("use_texture_modality needs the HIP library: the oracle's context has no texture modality")
         body = generator.Body(api, name, os.path.join(dataset_directory, "models", name, "textured.obj"), 1.0, True,
                               True, np.eye(4, dtype=F))
         models = []
@@ -950,7 +990,11 @@ def evaluate_ycb_dataset(open_context, dataset_directory, external_directory, se
         region_modality = host.RegionModality(api, body, color, models[0], depth_camera=depth, measure_occlusions=1,
                                               **region_parameters)
         depth_modality = host.DepthModality(api, body, depth, models[1], measure_occlusions=1, **depth_parameters)
-        host.Optimizer(api, body=body, modalities=[region_modality, depth_modality],
+        modalities = [region_modality, depth_modality]
+        if use_texture_modality:
+            modalities.append(_dataset_texture_modality(api, body, color, depth if measure_occlusions_texture else None,
+                                                        texture_parameters, detector_parameters))
+        host.Optimizer(api, body=body, modalities=modalities,
                        tikhonov_parameter_rotation=tikhonov_parameter_rotation,
                        tikhonov_parameter_translation=tikhonov_parameter_translation)
         tracker = host.Tracker(api, n_corr_iterations, n_update_iterations)
@@ -1010,6 +1054,13 @@ OPT_REGION_PARAMETERS = dict(  # evaluate_opt_dataset.cpp:24-40
 OPT_DEPTH_PARAMETERS = dict(  # evaluate_opt_dataset.cpp:41-48
     n_points_max=200, use_adaptive_coverage=0, use_depth_scaling=0, stride_length=0.005,
     considered_distances=[0.05, 0.02, 0.01], standard_deviations=[0.035, 0.035, 0.025])
+# evaluate_opt_dataset.cpp:49-77: YCB's fields with other standard deviations; no measured occlusions (opt_evaluator.cpp:
+# 314-326), so the two occlusion fields are not restated
+OPT_TEXTURE_PARAMETERS = dict(
+    focused_image_size=200, descriptor_distance_threshold=0.7, tukey_norm_constant=20.0,
+    standard_deviations=[5.0, 1.0, 0.5],
+    max_keyframe_rotation_difference=float(F(10.0) * F(np.pi) / F(180.0)), max_keyframe_age=1000, n_keyframes=1)
+OPT_DETECTOR_PARAMETERS = dict(n_features=300)  # set_orb_n_features(300), :58
 OPT_MODEL_PARAMETERS = dict(sphere_radius=0.8, n_divides=4, n_points=500, max_radius_depth_offset=0.05,
                             stride_depth_offset=0.002, use_random_seed=False, image_size=2000)  # opt_evaluator.cpp:531-543
 OPT_TIKHONOV_PARAMETER_ROTATION = 1000.0      # evaluate_opt_dataset.cpp:78-79
@@ -1242,8 +1293,10 @@ def evaluate_opt_dataset(open_context, dataset_directory, external_directory, bo
                          n_corr_iterations=OPT_N_CORR_ITERATIONS, n_update_iterations=OPT_N_UPDATE_ITERATIONS,
                          report=None, shard=(0, 1), batch=1, n_vertices_evaluation=1000, calculate_diameters=True,
                          diameters=None, intrinsics=OPT_INTRINSICS, depth2color_pose=OPT_DEPTH2COLOR_POSE,
-                         judge_on_device=False):
-    """OPTEvaluator::SetUp + Evaluate in the Region + Depth configuration (set_use_texture_modality(false)): one run per
+                         judge_on_device=False, use_texture_modality=False, texture_parameters=None,
+                         detector_parameters=None):
+    """OPTEvaluator::SetUp + Evaluate, by default in the Region + Depth configuration (the reference's example runs
+    Region + Depth + Texture, evaluate_opt_dataset.cpp:93-95: that is use_texture_modality below): one run per
     (body, orientation, motion pattern) (CreateRunConfigurations :499-511) on `dataset/3D/<sequence>/color|depth/
     NNNN.png` from image 1 (loader cameras :261-271, depth scale 0.001, the depth camera's camera2world the
     depth-to-colour pose), ground truth `dataset/3D/poses/<sequence>.txt`, bodies `dataset/Model3D/<body>/<body>.obj`
@@ -1255,11 +1308,19 @@ def evaluate_opt_dataset(open_context, dataset_directory, external_directory, bo
     batch: up to `batch` bodies share one context, each with its own cameras and its own list of this process's
     sequences, through evaluate_opt_sequences (one body per context: batch = 1).  shard = (rank, world): every world-th
     run.  Returns {sequence name: average result}, and the averages per body and over "all" bodies of all their frames
-    (CalculateAverageBodyResult :402-415)."""
+    (CalculateAverageBodyResult :402-415).
+    use_texture_modality (HIP library; set_use_texture_modality(true)): every body also gets the texture modality of
+    opt_evaluator.cpp:314-326 (_dataset_texture_modality, no measured occlusions) with OPT_TEXTURE_PARAMETERS overridden
+    by `texture_parameters` and the library's BUILT-IN DETECTOR (OPT_DETECTOR_PARAMETERS overridden by
+    `detector_parameters`) -- not ORB: the reference's configuration with another detector, whose AUC is not claimed to
+    equal the reference's.  The modality stands on the optimizer behind the region and the depth modality; in a batch,
+    Tracker.ResetBodies restarts it with its body.  With the oracle's context: ValueError."""
     import os
 
     from . import config as cfg
     from . import generator, host
+    texture_parameters = dict(OPT_TEXTURE_PARAMETERS, **(texture_parameters or {}))
+    detector_parameters = dict(OPT_DETECTOR_PARAMETERS, **(detector_parameters or {}))
     region_parameters = dict(OPT_REGION_PARAMETERS, **(region_parameters or {}))
     depth_parameters = dict(OPT_DEPTH_PARAMETERS, **(depth_parameters or {}))
     model_parameters = dict(OPT_MODEL_PARAMETERS, **(model_parameters or {}))
@@ -1274,6 +1335,8 @@ def evaluate_opt_dataset(open_context, dataset_directory, external_directory, bo
     for first in range(0, len(names), max(1, batch)):
         chunk = names[first:first + max(1, batch)]
         api = open_context()
+        if use_texture_modality and not getattr(api, "is_hip", True):  # (before a model is read or generated)
+            raise ValueError("use_texture_modality needs the HIP library: the oracle's context has no texture modality")
         bodies, evaluations, cameras, gt = [], [], [], []
         for name in chunk:
             geometry2body = opt_geometry2body_pose(name) if name in OPT_GEOMETRY2BODY_TRANSLATIONS else np.eye(4, dtype=F)
@@ -1294,7 +1357,11 @@ def evaluate_opt_dataset(open_context, dataset_directory, external_directory, bo
                                                 4, camera2world_pose=depth2color_pose)
             region_modality = host.RegionModality(api, body, color, models[0], **region_parameters)
             depth_modality = host.DepthModality(api, body, depth, models[1], **depth_parameters)
-            host.Optimizer(api, body=body, modalities=[region_modality, depth_modality],
+            modalities = [region_modality, depth_modality]
+            if use_texture_modality:
+                modalities.append(_dataset_texture_modality(api, body, color, None, texture_parameters,
+                                                            detector_parameters))
+            host.Optimizer(api, body=body, modalities=modalities,
                            tikhonov_parameter_rotation=tikhonov_parameter_rotation,
                            tikhonov_parameter_translation=tikhonov_parameter_translation)
             diameter = vertices_diameter(api, body.vertices) if calculate_diameters else diameters[name]

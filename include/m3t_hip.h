@@ -284,6 +284,12 @@ int m3t_hip_depth_modality_use_silhouette_checking(m3t_hip_context*, int modalit
  *   distance, the LOWER index first among equal distances (cv::BFMatcher::knnMatch(k = 2)); fewer than two current
  *   descriptors: no match; a query is kept iff NOT float(d0) / float(d1) >= descriptor_distance_threshold in f32 (0 / 0
  *   is NaN and kept, as in the reference).  Data points: keyframe after keyframe, query after query.
+ *   The match runs tiled: a (modality, ring slot x tile of 64 queries) grid finds every keyframe descriptor's best two
+ *   into 12 bytes of scratch per ring entry (n_keyframes x 4096 x 12 bytes per Hamming modality, n_keyframes the largest
+ *   among them), a collect launch of one workgroup per modality applies the ratio test in keyframe-then-query order
+ *   (m3t_texture_tiled.hip).  The developer override M3T_HIP_TEXTURE_MATCH=one in the environment, looked at once when
+ *   a context is created, keeps the one-workgroup matcher of m3t_texture.hip instead ("tiled" and "auto" name the
+ *   default; anything else is taken as "auto").  Both forms give the same bits.
  * texture_modality_get_points: data_points_ of the last CalculateCorrespondences / CalculateGradientAndHessian.
  * texture_modality_get_keyframes: how many keyframes are held, keyframe_age_, the points per keyframe (oldest first;
  *   8 ints) and, unless points_xyz is NULL, the points themselves, keyframe after keyframe (capacity_points x 3 floats;

@@ -38,7 +38,7 @@ def summary(values):
 
 
 class Body:
-    def __init__(self, api, camera, n_bytes, with_region=False):
+    def __init__(self, api, camera, n_bytes, with_region=False, n_keyframes=1):
         self.body = host.Body(api, mtv.body2world())
         tv, tf = pkg.config.load_obj(os.path.join(GOLDEN, "_body", "triangle.obj"))
         self.body.set_geometry(tv, tf, np.asarray(mtv.GEOMETRY2BODY, F), body_id=150, region_id=150)
@@ -46,7 +46,8 @@ class Body:
         geometry.AddBody(self.body)
         self.renderer = host.FocusedSilhouetteRenderer(api, geometry, camera, id_type=0)
         self.renderer.AddReferencedBody(self.body)
-        self.texture = host.TextureModality(api, self.body, camera, self.renderer, descriptor_bytes=n_bytes)
+        self.texture = host.TextureModality(api, self.body, camera, self.renderer, descriptor_bytes=n_bytes,
+                                            n_keyframes=n_keyframes)
         modalities = [self.texture]
         if with_region:
             v = np.load(os.path.join(ROOT, "tests", "golden", "triangle_views.npz"))
