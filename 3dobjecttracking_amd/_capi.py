@@ -409,6 +409,8 @@ _HIP_ONLY = {
     "cameras_upload_batch_roi_async": [c_int_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_size_t],
     "roi_get_status": [c_int_p, C.c_int, c_int_p, C.POINTER(C.c_longlong)],
     "roi_get_unrecovered": [c_int_p, C.c_int, c_int_p],
+    "roi_get_rectangles": [c_int_p, C.c_int, C.c_int, c_int_p],
+    "camera_download_slot": [C.c_int, C.c_int, C.c_void_p, C.c_size_t],
     "reserve_ingest_cus": [C.c_int],
     "camera_select_slot": [C.c_int, C.c_int],
     "cameras_select_slot": [C.c_int],
@@ -469,7 +471,7 @@ def pose_ret(buf):
 
 
 _NEWER_ENTRY_POINTS = ("comm_set_reduce_callback", "get_step_kernel", "get_step_variant", "comm_get_allreduce_count", "comm_get_rank_count", "debug_log_checksum", "set_roi_ingest",
-                       "cameras_upload_batch_roi_async", "roi_get_status", "roi_get_unrecovered", "reserve_ingest_cus", "camera_slot_sync",
+                       "cameras_upload_batch_roi_async", "roi_get_status", "roi_get_unrecovered", "roi_get_rectangles", "camera_download_slot", "reserve_ingest_cus", "camera_slot_sync",
                        "texture_modality_set_detector", "texture_modality_get_features", "texture_modality_get_focused_image",
                        "texture_modality_create_l2")
 

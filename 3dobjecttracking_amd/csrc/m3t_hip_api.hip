@@ -2801,6 +2801,38 @@ int m3t_hip_roi_get_unrecovered(m3t_hip_context* ctx, int* bodies, int capacity,
   *n = 0;
   return ReadRoiMisses(ctx, true, bodies, capacity, n);
 }
+// Developer read-backs (tests/test_gpu_roi_edges.py): what the ROI kernels left on the device, read behind the copy
+// streams and the compute stream.  Nothing is launched and no state of the context changes.
+int m3t_hip_roi_get_rectangles(m3t_hip_context* ctx, const int* ids, int n, int slot, int* rects) {
+  CHECK_CTX();
+  REQUIRE(ids && n >= 1 && rects, M3T_ERR_INVALID_ARGUMENT, "bad arguments");
+  REQUIRE(ctx->roi_enabled && ctx->n_roi_items > 0 && !ctx->tables_dirty && ctx->d_roi_rects.p, M3T_ERR_UNSUPPORTED,
+          "roi_get_rectangles: no rectangle table (ROI ingest off, or the tables were not built by a step yet)");
+  for (int i = 0; i < n; ++i)
+    REQUIRE(ids[i] >= 0 && ids[i] < int(ctx->cameras.size()), M3T_ERR_INVALID_ARGUMENT, "bad camera id");
+  REQUIRE(slot >= 0 && slot < ctx->roi_rect_slots, M3T_ERR_INVALID_ARGUMENT, "bad frame slot");
+  HIPCHK(hipSetDevice(ctx->device));
+  HIPCHK(ctx->ingest.SyncCopies());
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  static_assert(sizeof(m3t_roi_rect) == 4 * sizeof(int), "a rectangle is x0 y0 x1 y1");
+  const m3t_roi_rect* table = ctx->d_roi_rects.as<m3t_roi_rect>() + size_t(slot) * ctx->cameras.size();
+  for (int i = 0; i < n; ++i)
+    HIPCHK(hipMemcpy(rects + 4 * i, table + ids[i], sizeof(m3t_roi_rect), hipMemcpyDeviceToHost));
+  return M3T_OK;
+}
+int m3t_hip_camera_download_slot(m3t_hip_context* ctx, int id, int slot, void* pixels, size_t row_step) {
+  CHECK_CTX();
+  REQUIRE(id >= 0 && id < int(ctx->cameras.size()) && pixels, M3T_ERR_INVALID_ARGUMENT, "bad camera id");
+  const Camera& c = *ctx->cameras[id];
+  REQUIRE(slot >= 0 && slot < c.n_slots, M3T_ERR_INVALID_ARGUMENT, "bad frame slot");
+  const size_t row = size_t(c.intr.width) * (c.is_depth ? 2 : 3);
+  REQUIRE(row_step >= row, M3T_ERR_INVALID_ARGUMENT, "row_step smaller than one image row");
+  HIPCHK(hipSetDevice(ctx->device));
+  HIPCHK(ctx->ingest.SyncCopies());
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  HIPCHK(hipMemcpy2D(pixels, row_step, c.frame(slot), c.pitch, row, size_t(c.intr.height), hipMemcpyDeviceToHost));
+  return M3T_OK;
+}
 int m3t_hip_ingest_sync(m3t_hip_context* ctx) {
   CHECK_CTX();
   HIPCHK(hipSetDevice(ctx->device));

@@ -26,14 +26,19 @@
 #endif
 
 typedef struct m3t_roi_rect {
-  int x0, y0, x1, y1;  // inclusive pixel bounds; empty when x1 < x0
+  int x0, y0, x1, y1;  // inclusive pixel bounds; empty when x1 < x0 or y1 < y0 (m3t_roi_is_empty)
 } m3t_roi_rect;
 
 M3T_ROI_FN m3t_roi_rect m3t_roi_empty(void) {
   m3t_roi_rect r = {1 << 30, 1 << 30, -(1 << 30), -(1 << 30)};
   return r;
 }
+M3T_ROI_FN int m3t_roi_is_empty(m3t_roi_rect r) { return r.x1 < r.x0 || r.y1 < r.y0; }
+// (an empty operand does not widen the union: a body wholly off the frame comes out of m3t_roi_widen clipped to
+// x1 = width - 1 < x0 or y1 = height - 1 < y0, which is empty but not the neutral element of min / max)
 M3T_ROI_FN m3t_roi_rect m3t_roi_union(m3t_roi_rect a, m3t_roi_rect b) {
+  if (m3t_roi_is_empty(b)) return a;
+  if (m3t_roi_is_empty(a)) return b;
   m3t_roi_rect r;
   r.x0 = a.x0 < b.x0 ? a.x0 : b.x0;
   r.y0 = a.y0 < b.y0 ? a.y0 : b.y0;
@@ -42,7 +47,8 @@ M3T_ROI_FN m3t_roi_rect m3t_roi_union(m3t_roi_rect a, m3t_roi_rect b) {
   return r;
 }
 M3T_ROI_FN int m3t_roi_contains(m3t_roi_rect outer, m3t_roi_rect inner) {
-  return inner.x1 < inner.x0 || (outer.x0 <= inner.x0 && outer.y0 <= inner.y0 && outer.x1 >= inner.x1 && outer.y1 >= inner.y1);
+  // (nothing is needed of an empty rectangle -- a body off the frame above or below is empty in y alone)
+  return m3t_roi_is_empty(inner) || (outer.x0 <= inner.x0 && outer.y0 <= inner.y0 && outer.x1 >= inner.x1 && outer.y1 >= inner.y1);
 }
 
 // a window of the reference's strided scans around a centre: rounded_radius + the roundings of its corners

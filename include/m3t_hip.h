@@ -162,6 +162,15 @@ int m3t_hip_cameras_upload_batch_roi_async(m3t_hip_context*, const int* camera_i
 int m3t_hip_roi_get_status(m3t_hip_context*, int* body_ids, int capacity, int* n_misses,
                             long long* n_rectangle_uploads /* batch-frames that went as rectangles so far; may be NULL */);
 int m3t_hip_roi_get_unrecovered(m3t_hip_context*, int* body_ids, int capacity, int* n_bodies);
+/* Developer read-backs of what ROI ingest left on the device, both behind the copy streams and the compute stream;
+ * they launch nothing and change nothing.  roi_get_rectangles: the rectangle table of ring slot `slot` for the n
+ * cameras listed, x0 y0 x1 y1 each (inclusive; x1 < x0 or y1 < y0: empty -- a body off the frame below, alone in its
+ * camera, reads x0 <= x1 with y0 > y1 = height - 1; the whole frame after a whole-frame upload or a repair).
+ * M3T_ERR_INVALID_ARGUMENT for a bad id or slot, M3T_ERR_UNSUPPORTED for a context without ROI tables (ROI ingest off,
+ * or no step has built them since the last change).  camera_download_slot: the rows of that ring slot of one camera,
+ * width * bytes per pixel each, row_step apart. */
+int m3t_hip_roi_get_rectangles(m3t_hip_context*, const int* camera_ids, int n_cameras, int slot, int* rects);
+int m3t_hip_camera_download_slot(m3t_hip_context*, int camera_id, int slot, void* pixels, size_t row_step);
 /* Keep n_cus compute units free of the tracking kernels and run the ROI pull kernel on them (CU-masked streams), so
  * that the rectangles of frame k + 1 cross PCIe WHILE step k runs: on shared CUs the pull's PCIe reads hold the CUs'
  * memory pipelines and the step takes 2.3-3 x longer, on CUs of its own the pull costs the step little.  n_cus has to

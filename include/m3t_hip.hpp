@@ -107,6 +107,9 @@ class Camera {
   }
   bool SelectSlot(int slot) { return c_->Step(m3t_hip_camera_select_slot(c_->get(), id_, slot)); }
   bool SlotSync(int slot) { return c_->Step(m3t_hip_camera_slot_sync(c_->get(), id_, slot)); }  // this camera's copy only
+  bool DownloadSlot(int slot, void* pixels, size_t row_step) {  // developer read-back of a ring slot
+    return c_->Step(m3t_hip_camera_download_slot(c_->get(), id_, slot, pixels, row_step));
+  }
   int id() const { return id_; }
 
  protected:
@@ -697,6 +700,12 @@ class Tracker {
     c_->Check(m3t_hip_roi_get_unrecovered(c_->get(), bodies.data(), int(bodies.size()), &n), "Tracker");
     bodies.resize(size_t(n < int(bodies.size()) ? n : int(bodies.size())));
     return bodies;
+  }
+  // developer read-back: the rectangles (x0 y0 x1 y1 each) of ring slot `slot` for the cameras listed
+  std::vector<int> RoiRectangles(const std::vector<int>& camera_ids, int slot) {
+    std::vector<int> rects(camera_ids.size() * 4);
+    c_->Check(m3t_hip_roi_get_rectangles(c_->get(), camera_ids.data(), int(camera_ids.size()), slot, rects.data()), "Tracker");
+    return rects;
   }
   // a kinematic structure spread over GPUs: begin -> all-reduce(sum) of `count` floats at `partial` on stream() -> end
   bool CalculateOptimizationBegin(float** partial, size_t* count) {

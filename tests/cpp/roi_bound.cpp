@@ -16,6 +16,25 @@ void roi_region_depth(const float* body2camera, const float* box_min, const floa
   m3t_roi_region_depth_reach(p, &reach_m, &reach_px);
   put(m3t_roi_body(body2camera, box_min, box_max, intr, reach_px, reach_m, rho), out);
 }
+// tests/test_roi_reference.py: a reader with its reaches given, the union of two rectangles, the reaches themselves
+void roi_body(const float* body2camera, const float* box_min, const float* box_max, const m3t_intrinsics* intr,
+              float reach_px, float reach_m, float rho, int* out) {
+  put(m3t_roi_body(body2camera, box_min, box_max, intr, reach_px, reach_m, rho), out);
+}
+void roi_union(const int* a, const int* b, int* out) {
+  put(m3t_roi_union(m3t_roi_rect{a[0], a[1], a[2], a[3]}, m3t_roi_rect{b[0], b[1], b[2], b[3]}), out);
+}
+void roi_empty(int* out) { put(m3t_roi_empty(), out); }
+int roi_contains(const int* outer, const int* inner) {
+  return m3t_roi_contains(m3t_roi_rect{outer[0], outer[1], outer[2], outer[3]}, m3t_roi_rect{inner[0], inner[1], inner[2], inner[3]});
+}
+void roi_reaches(const m3t_region_modality_params* rp, const m3t_depth_modality_params* dp, float fu, int corr_iteration,
+                 float* out /* line, histogram, region depth m, px, depth m, px */) {
+  out[0] = m3t_roi_region_line_reach(rp, corr_iteration);
+  out[1] = m3t_roi_region_histogram_reach(rp);
+  m3t_roi_region_depth_reach(rp, &out[2], &out[3]);
+  m3t_roi_depth_reach(dp, fu, &out[4], &out[5]);
+}
 void roi_depth(const float* body2camera, const float* box_min, const float* box_max, const m3t_intrinsics* intr,
                const m3t_depth_modality_params* p, float rho, int* out) {
   float reach_m, reach_px;

@@ -1,5 +1,5 @@
 """The L2 texture modality's part of the C-ABI and of the configuration front-end on the CPU: the new entry point is
-declared, HIP-only and exported beside the others (130 in all); GenerateConfiguredTracker takes descriptor_type SIFT and
+declared, HIP-only and exported beside the others (132 in all); GenerateConfiguredTracker takes descriptor_type SIFT and
 DAISY with the caller's detector and l2_descriptors=True and sizes the descriptors (a recording stand-in for the device
 context shows what it would create), and refuses them without the opt-in as it did; host.TextureModality refuses descriptors of another dtype or width before anything is called."""
 import ctypes
@@ -30,7 +30,7 @@ def test_the_entry_point_is_declared_hip_only_and_exported():
     exported = [line.split()[-1] for line in subprocess.check_output(["nm", "-D", "--defined-only", util.pkg.LIB_PATH],
                                                                      text=True).splitlines()]
     exported = [s for s in exported if s.startswith("m3t_hip_")]
-    assert len(exported) == len(set(exported)) == 130
+    assert len(exported) == len(set(exported)) == 132
     assert set(exported) == set(re.findall(r"\b(m3t_hip_\w+)\(", header))
 
 
